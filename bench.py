@@ -1,6 +1,6 @@
 """Headline benchmark: hammer-v0 env-steps/s on N MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu E] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,6 +20,12 @@ episode and reset on every step, and all episode phases are present.  Every `hor
 are all-gathered over RCCL / xGMI -- every finished episode is counted once, whenever it
 ended.  Weak scaling: envs per GPU fixed (default 65 536 = the north-star configuration).
 Inputs are resident in HBM; value = N * envs_per_gpu * K / max-over-ranks wall time.
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the result line.  `--full`
+adds the legs that take runs of their own after the timed window: the one-step parity of the
+timed handle against the fp64 oracle, the auxiliary 4 096-env figure and the CPU baseline (each
+can be switched off there with its `--no-...` option).  `--dump-outputs DIR` writes what the last
+timed step left in the caller's buffers (`dump_outputs`).
 """
 import argparse
 import json
@@ -214,6 +220,28 @@ def same_run_parity(blob, sim, n=256, model=None, pol=None, obs_now=None):
                 tolerance="qpos 2e-5 + 1e-5|q|, qvel 5e-3 (1 + |v|) per env (tests/test_gpu_parity.py)")
 
 
+DUMP_BUDGET = 60 * 10 ** 6      # bytes of --dump-outputs arrays in all (the limit is 64 MB)
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: the per-env device arrays `arrays` (name -> tensor [n, ...]) as
+    path/<name>.npy in float32.  When they exceed DUMP_BUDGET together, the same sorted sample of
+    envs (numpy Generator, fixed seed) is kept of every array; path/env_index.npy (float64) holds
+    the env index of each row either way."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    row = 8 + sum(4 * a[0].numel() for a in arrays.values())
+    idx = np.arange(n)
+    if n * row > DUMP_BUDGET:
+        idx = np.sort(np.random.default_rng(seed).choice(n, DUMP_BUDGET // row, replace=False))
+    for name, a in arrays.items():
+        sel = a if len(idx) == n else a[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), sel.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
+
+
 def config2(blob, env_id, device, n=4096, steps=100, warmup=10):
     """BASELINE configs[1] (hammer-v0, 4 096 envs, random policy) as an auxiliary figure."""
     import torch
@@ -318,11 +346,17 @@ def main():
     ap.add_argument("--total-envs", type=int, default=0,
                     help="strong scaling: fixed total envs split over the ranks (e.g. 262144, SURVEY C4)")
     ap.add_argument("--env", default=ENV_ID)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also run the one-step parity against the fp64 oracle, the "
+                         "auxiliary 4 096-env figure and the CPU baseline (one GPU only); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step left with the caller (obs, reward, done, goal, "
+                         "the step's actions, rank 0's per-env episode totals) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the one-step parity")
     ap.add_argument("--no-config2", action="store_true",
-                    help="skip the auxiliary 4 096-env figure (profiling runs: every k_step launch is then "
-                         "the headline size, so rocprof's average matches roofline.kernel_ms)")
+                    help="with --full: skip the auxiliary 4 096-env figure (profiling runs: every k_step launch "
+                         "is then the headline size, so rocprof's average matches roofline.kernel_ms)")
     ap.add_argument("--policy", choices=("none", "random-mlp", "dapg"), default="none",
                     help="closed loop: actions from the on-device Gaussian MLP (k_mlp): random init 32x32 "
                          "(sampled), or the reference's pretrained DAPG policy (mean action)")
@@ -456,6 +490,12 @@ def main():
     kern_ms = sum(kern) / args.steps
     depth_ms = sum(e[2].elapsed_time(e[3]) for e in events) / args.steps if depth is not None else None
     e1, r1, s1 = gather()
+    if args.dump_outputs and rank == 0:
+        out = dict(obs=obs, reward=rew, done=done, goal=goal, action=act, episode_count=tot_ep,
+                   episode_return=tot_ret, episode_success=tot_suc)
+        if depth is not None:
+            out["depth"] = depth
+        dump_outputs(args.dump_outputs, out)
     # the exchange's own check: the gathered global totals equal the sum of every rank's block
     rank_sums = torch.stack([tot_ep.long().sum(), tot_suc.long().sum()])
     if pg:
@@ -556,17 +596,17 @@ def main():
                                          "(nconmax / njmax, DAPG_assets.xml:4); wide_tier_envs: envs with >= 1 "
                                          "env-step past the fast tier's capacities, re-run in the wide tier"),
                     episodes=episodes, exchange=exchange)
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             try:
                 line["parity_one_step"] = same_run_parity(blob, sim, model=m, pol=pol, obs_now=obs)
                 line["parity_one_step"]["actions"] = ("the policy's mean action on the current obs" if pol is not None
                                                       else "Philox U(-1, 1)")
             except Exception as e:
                 line["parity_one_step"] = dict(error=str(e))
-        if world == 1 and env_id == ENV_ID and depth is None and pol is None and n == 65536 \
+        if args.full and world == 1 and env_id == ENV_ID and depth is None and pol is None and n == 65536 \
                 and not args.no_config2:
             line["config2_4096_envs"] = config2(blob, env_id, local)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(blob, env_id, local)
             except Exception as e:  # the baseline must not hide the GPU number

@@ -10,7 +10,6 @@ if REPO not in sys.path:
 
 ENVS = ["hammer-v0", "door-v0", "pen-v0", "relocate-v0"]
 GOLDEN = os.path.join(REPO, "tests", "golden")
-REFERENCE = "/root/reference"
 
 
 def pytest_configure(config):

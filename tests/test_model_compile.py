@@ -4,7 +4,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import ENVS, REFERENCE
+from conftest import ENVS, GOLDEN
 
 # (nq, nu, obs_dim, frame_skip, horizon, nbody) -- SURVEY §2 per-task table; obs/act dims are
 # also pinned by the DAPG pickles' param_shapes (46/26, 39/28, 45/24, 39/30)
@@ -63,13 +63,13 @@ def test_pen_inertia_from_geoms():
     assert m.body_mass[b] == pytest.approx(pen + top + bot + cli, rel=1e-12)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference MJCF not mounted")
 @pytest.mark.parametrize("env_id", ENVS)
 def test_committed_model_matches_fresh_compile(env_id):
+    """the committed model tables against a fresh compile of the reference's MJCF scenes
+    (tests/golden/mjcf: the task files and the two files they include, stored as fixtures)"""
     from mj_envs_amd.mjcf import compile_mjcf
     from mj_envs_amd.tasks import TASKS, load_model
-    fresh = compile_mjcf(os.path.join(REFERENCE, "mj_envs_vision/hand_manipulation_suite/assets",
-                                      TASKS[env_id].xml))
+    fresh = compile_mjcf(os.path.join(GOLDEN, "mjcf", TASKS[env_id].xml))
     m = load_model(env_id)
     assert fresh.dims == m.dims
     for k, v in fresh.arrays.items():

@@ -11,7 +11,7 @@ for rep in 1 2; do
   for v in "$@"; do
     LIB=mj_envs_amd/libadroit_hip_$v.so
     [ "$v" = "main" ] && LIB=mj_envs_amd/libadroit_hip.so
-    AW_LIB=$LIB timeout -k 10 200 python bench.py --steps 200 --policy $POL --no-cpu-baseline --no-config2 $BENCH_ARGS \
+    AW_LIB=$LIB timeout -k 10 200 python bench.py --full --steps 200 --policy $POL --no-cpu-baseline --no-config2 $BENCH_ARGS \
       > gpurun_out/ab/${POL}_${v}_$rep.json 2> gpurun_out/ab/${POL}_${v}_$rep.err
     python -c "import json;d=json.load(open('gpurun_out/ab/${POL}_${v}_$rep.json'));p=d.get('parity_one_step',{});print('$POL $v rep$rep', d['value'], d['roofline']['kernel_ms'], 'parity', p.get('frac_within_tol'), 'success', d['episodes']['success_pct'], 'wide', d.get('wide_tier_envs'), 'overflow', d.get('overflow_envs'))"
   done

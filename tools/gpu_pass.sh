@@ -15,14 +15,14 @@ echo "[pass] smoke"
 timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 cat $OUT/smoke.log
 echo "[pass] bench"
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 echo "[pass] bench dapg"
-timeout -k 10 300 python bench.py --policy dapg --steps 200 --no-cpu-baseline --no-config2 > $OUT/bench_dapg.json 2> $OUT/bench_dapg.err
+timeout -k 10 300 python bench.py --full --policy dapg --steps 200 --no-cpu-baseline --no-config2 > $OUT/bench_dapg.json 2> $OUT/bench_dapg.err
 echo "[pass] config 3"
 for e in door-v0 pen-v0 relocate-v0; do
-  timeout -k 10 200 python bench.py --env $e --envs-per-gpu 16384 --steps 200 --no-cpu-baseline >> $OUT/bench_config3.jsonl 2>> $OUT/bench_config3.err
+  timeout -k 10 200 python bench.py --full --env $e --envs-per-gpu 16384 --steps 200 --no-cpu-baseline >> $OUT/bench_config3.jsonl 2>> $OUT/bench_config3.err
 done
 echo "[pass] config 5"
-timeout -k 10 200 python bench.py --depth --steps 200 --no-cpu-baseline > $OUT/bench_depth.json 2> $OUT/bench_depth.err
+timeout -k 10 200 python bench.py --full --depth --steps 200 --no-cpu-baseline > $OUT/bench_depth.json 2> $OUT/bench_depth.err
 echo "[pass] done"

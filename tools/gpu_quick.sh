@@ -13,10 +13,10 @@ tail -5 $OUT/pytest_gpu.log
 case $rc in 0|1) ;; *) echo "pytest rc $rc: stopping"; exit $rc;; esac
 if [ -z "$NO_BENCH" ]; then
 echo "[quick] bench"
-timeout -k 10 300 python bench.py --steps 100 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --steps 100 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 echo "[quick] config 3 relocate"
-timeout -k 10 200 python bench.py --env relocate-v0 --envs-per-gpu 16384 --steps 200 --no-cpu-baseline > $OUT/bench_relocate.json 2> $OUT/bench_relocate.err
+timeout -k 10 200 python bench.py --full --env relocate-v0 --envs-per-gpu 16384 --steps 200 --no-cpu-baseline > $OUT/bench_relocate.json 2> $OUT/bench_relocate.err
 cat $OUT/bench_relocate.json
 fi
 echo "[quick] done"
