@@ -305,8 +305,14 @@ struct Dof {
 // follows the LDS overlays (aw_common.h Env): the constraint rows are assembled while the
 // phase-K arrays (cdof, subcom) are alive, then the solver phase reuses that storage.
 // ROWST (aw_forward_dump only): the Newton solve's final row states (S_*) go to rowst[r]
+// touch: evaluate the touch sensors (AW_TOUCH_LAST: only the forwards whose s.touch is read -- the
+// env-step's last substep, the reset / DK_FORWARD forward, the dump and test kernels)
+#ifndef AW_TOUCH_LAST
+#define AW_TOUCH_LAST 1
+#endif
 template <int TASK, bool ROWST = false>
-AW_DEV void forward(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>::NV], Dof& d, float* rowst = nullptr) {
+AW_DEV void forward(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>::NV], Dof& d, float* rowst = nullptr,
+                    bool touch = true) {
   constexpr int NV = Tree<TASK>::NV;
   stage_kinematics(m, s, lane);
   AW_PROF(s, PR_KIN);
@@ -328,6 +334,8 @@ AW_DEV void forward(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>:
     for (int k = 0; k < NV; k++) row[k] = Mrow[k];
     float invd;
     tree_factor<TASK>(row, invd, lane);
+    // noslip inverts the same M: it reloads this factor instead of factoring again (AW_MFAC_HANDOFF)
+    if (AW_MFAC_HANDOFF && s.nefc != 0 && noslip_on(m)) mfac_store<NV>(m, s, lane, row, invd);
     d.qacc_smooth = tree_solve<TASK>(row, invd, d.qfrc_smooth, lane);
   }
   AW_PROF(s, PR_SMOOTH);
@@ -338,7 +346,7 @@ AW_DEV void forward(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>:
     float a = 0.f;
     solve_newton<NV, ROWST>(m, s, lane, Mrow, a, d.qfrc_smooth, d.qacc_smooth, rowst);
     AW_PROF(s, PR_NEWTON);
-    if (m.noslip_iterations > 0 && !(m.disableflags & DSBL_NOSLIP)) solve_noslip<TASK>(m, s, lane, Mrow, a);
+    if (noslip_on(m)) solve_noslip<TASK>(m, s, lane, Mrow, a);
     AW_PROF(s, PR_NOSLIP);
     for (int r = lane; r < s.nefc; r += 64) s.rowbuf[r] = s.efc_force[r];
     wsync();
@@ -346,7 +354,7 @@ AW_DEV void forward(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>:
     d.qacc = lane < NV ? a : 0.f;
     d.qfrc_con = lane < NV ? qc : 0.f;
   }
-  stage_touch(m, s, lane);
+  if (!AW_TOUCH_LAST || touch) stage_touch(m, s, lane);
   AW_PROF(s, PR_JT_TOUCH);
 }
 
@@ -426,25 +434,25 @@ AW_DEV bool check_acc(Env& s, int lane, const Dof& d) {
 template <int NV>
 AW_DEV void load_env(const DModel& m, Env& s, const DState& st, int env, int lane) {
   if (lane < NV) {
-    s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane];
+    s.qpos[lane] = GIN(st.qpos)[(size_t)env * m.nq + lane];
     s.qlo[lane] = 0.f;   // the stored state is fp32: the env-step starts from it exactly
-    s.qvel[lane] = st.qvel[(size_t)env * m.nv + lane];
-    s.warm[lane] = st.warm[(size_t)env * m.nv + lane];
+    s.qvel[lane] = GIN(st.qvel)[(size_t)env * m.nv + lane];
+    s.warm[lane] = GIN(st.warm)[(size_t)env * m.nv + lane];
   }
   if (lane == 0) { s.status = 0u; s.slot = blockIdx.x; }
 }
 template <int NV>
 AW_DEV void store_env(const DModel& m, Env& s, const DState& st, int env, int lane) {
   if (lane < NV) {
-    st.qpos[(size_t)env * m.nq + lane] = s.qpos[lane];
-    st.qvel[(size_t)env * m.nv + lane] = s.qvel[lane];
-    st.warm[(size_t)env * m.nv + lane] = s.warm[lane];
+    GOUT(st.qpos)[(size_t)env * m.nq + lane] = s.qpos[lane];
+    GOUT(st.qvel)[(size_t)env * m.nv + lane] = s.qvel[lane];
+    GOUT(st.warm)[(size_t)env * m.nv + lane] = s.warm[lane];
   }
 }
 AW_DEV void write_obs(const DModel& m, Env& s, int lane, float* out) {
   task_obs(m, s, lane, s.rowbuf);
   wsync();
-  for (int o = lane; o < m.obs_dim; o += 64) out[o] = s.rowbuf[o];
+  for (int o = lane; o < m.obs_dim; o += 64) GOUT(out)[o] = s.rowbuf[o];
   wsync();
 }
 
@@ -560,7 +568,7 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
     if (WIDE && el == 0) s.status = ST_WIDE;
     if (el < m.nu) {
       float c = 0.f;
-      if (kind == DK_STEP) c = MD(act_mid, el) + clampf(io.actions[(size_t)env * m.nu + el], -1.f, 1.f) * MD(act_rng, el);
+      if (kind == DK_STEP) c = MD(act_mid, el) + clampf(GIN(io.actions)[(size_t)env * m.nu + el], -1.f, 1.f) * MD(act_rng, el);
       s.ctrl[el] = c;
     }
     stage_model(m, s, st.params + (size_t)env * m.nparam, el);
@@ -581,7 +589,9 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
     const int sl = opaque(lane);
     if (!resetting && !retry) check_state<NV>(s, sl);
     AW_PROF(s, PR_CHECK);
-    forward<TASK>(m, s, sl, Mrow, d);
+    // s.touch is read by the observation only: after the last substep (its mj_checkAcc retry
+    // included) and after the reset forward
+    forward<TASK>(m, s, sl, Mrow, d, nullptr, resetting || sub + 1 >= m.frame_skip);
     if (fast_overflow(m, s)) {
       if (!resetting) {            // nothing of this env-step is written: the wide tier re-runs it
         defer_env(io.defer, env, DK_STEP, sl);
@@ -604,19 +614,19 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
       float r;
       int dn, gl;
       task_reward(m, s, &r, &dn, &gl);
-      io.reward[env] = r;
-      io.goal[env] = (uint8_t)gl;
-      int t = st.ep_len[env] + 1;
+      GOUT(io.reward)[env] = r;
+      GOUT(io.goal)[env] = (uint8_t)gl;
+      int t = GIN(st.ep_len)[env] + 1;
       term = dn;
       trunc = (m.horizon > 0 && t >= m.horizon) ? 1 : 0;
-      io.done[env] = (uint8_t)(term | (trunc << 1));
-      float ret = st.ep_ret[env] + r;
-      int gcount = st.ep_goal[env] + gl;
-      st.ep_len[env] = t;
-      st.ep_ret[env] = ret;
-      st.ep_goal[env] = gcount;
-      st.status[env] = s.status;
-      st.status_acc[env] |= s.status;
+      GOUT(io.done)[env] = (uint8_t)(term | (trunc << 1));
+      float ret = GIN(st.ep_ret)[env] + r;
+      int gcount = GIN(st.ep_goal)[env] + gl;
+      GOUT(st.ep_len)[env] = t;
+      GOUT(st.ep_ret)[env] = ret;
+      GOUT(st.ep_goal)[env] = gcount;
+      GOUT(st.status)[env] = s.status;
+      GOUT(st.status_acc)[env] |= s.status;
       if (term || trunc) {
         st.last_ret[env] = ret;
         st.last_goal[env] = gcount;
@@ -632,7 +642,7 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
     if (!(io.autoreset && ended)) break;
     __threadfence_block();
     if (float* tob = io.terminal_obs)
-      for (int o = tl; o < m.obs_dim; o += 64) tob[(size_t)env * m.obs_dim + o] = s.rowbuf[o];
+      for (int o = tl; o < m.obs_dim; o += 64) GOUT(tob)[(size_t)env * m.obs_dim + o] = s.rowbuf[o];
     wsync();
     reset_prepare<NV>(m, s, st, env, tl, nullptr, io.seed);
     if (WIDE && tl == 0) s.status |= ST_WIDE;
@@ -1183,6 +1193,7 @@ struct aw_handle {
   int grid_env = -1;         // AW_STEP_GRID at create (-1: unset)
   void* dmhdr_wide = nullptr;   // the wide tier's header: m with jspill -> jspill_wide, then st
   float* jspill_wide = nullptr; // one JSPILL_WIDE block per wide workgroup
+  float* mfac_wide = nullptr;   // one MFAC block per wide workgroup
   int wide_grid = 0;            // persistent k_step_wide workgroups (resident slots, capped at nenv)
   // aw_set_fault: the model table's pair margins / broadphase radii as built (restored by kind 0)
   std::vector<float> fault_margin0, fault_rb0;
@@ -1196,6 +1207,7 @@ static int upload_header(aw_handle* h) {
   HIPCHK(hipMemcpy((DModel*)h->dmhdr + 1, &h->st, sizeof(DState), hipMemcpyHostToDevice));
   DModel mw = h->m;
   mw.jspill = h->jspill_wide;
+  mw.mfac = h->mfac_wide;
   HIPCHK(hipMemcpy(h->dmhdr_wide, &mw, sizeof(DModel), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy((DModel*)h->dmhdr_wide + 1, &h->st, sizeof(DState), hipMemcpyHostToDevice));
   return AW_OK;
@@ -1546,6 +1558,7 @@ template <int TASK>
 static void launch_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, hipStream_t st) {
   DModel mw = h->m;
   mw.jspill = h->jspill_wide;   // the dense rows past JL in the wide tier's spill block (slot 0)
+  mw.mfac = h->mfac_wide;
   hipLaunchKernelGGL((k_dump_wide<TASK>), dim3(1), dim3(64), 0, st, mw, h->st, env, ctrl, out);
 }
 template <int TASK> const WideOps* wide_ops() {
@@ -1736,9 +1749,11 @@ static void free_handle(aw_handle* h) {
   if (h->dmhdr) (void)hipFree(h->dmhdr);
   if (h->dstate) (void)hipFree(h->dstate);
   if (h->m.jspill) (void)hipFree(h->m.jspill);
+  if (h->m.mfac) (void)hipFree(h->m.mfac);
   if (h->next_env) (void)hipFree(h->next_env);
   if (h->dmhdr_wide) (void)hipFree(h->dmhdr_wide);
   if (h->jspill_wide) (void)hipFree(h->jspill_wide);
+  if (h->mfac_wide) (void)hipFree(h->mfac_wide);
   delete h;
 }
 
@@ -1773,6 +1788,7 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   h->m.d = (const MData*)h->dmodel;
   // fast tier: one spill block per workgroup of k_reset / k_set_state (one per env)
   HIPCHK(hipMalloc((void**)&h->m.jspill, (size_t)n_envs * JSPILL_FAST * sizeof(float)));
+  HIPCHK(hipMalloc((void**)&h->m.mfac, (size_t)n_envs * MFAC * sizeof(float)));
   HIPCHK(hipMalloc(&h->dmhdr, sizeof(DModel) + sizeof(DState)));
   const size_t nq = 10 + 3 * (size_t)n_envs;   // + per-env costs and the claim permutation (k_order)
   HIPCHK(hipMalloc((void**)&h->next_env, nq * sizeof(int)));
@@ -1782,6 +1798,7 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   DISPATCH_TASK(h->m.task_kind, CALL)
 #undef CALL
   HIPCHK(hipMalloc((void**)&h->jspill_wide, (size_t)h->wide_grid * JSPILL_WIDE * sizeof(float)));
+  HIPCHK(hipMalloc((void**)&h->mfac_wide, (size_t)h->wide_grid * MFAC * sizeof(float)));
   HIPCHK(hipMalloc(&h->dmhdr_wide, sizeof(DModel) + sizeof(DState)));
   const size_t bytes = layout_state(h.get(), nullptr);   // dry run: sizes only
   HIPCHK(hipMalloc(&h->dstate, bytes));

@@ -111,6 +111,9 @@ extern __device__ unsigned long long g_stage_prof[];   // adroit_wave.hip (stage
 #endif
 namespace aw {
 constexpr int JSPILL_FAST = (FAST_MAXDENSE_ALLOC - 32) * VS, JSPILL_WIDE = (WIDE_MAXDENSE - 32) * VS;
+// floats per slot of the M-factor block (DModel::mfac): the forward's factor of M, [k][lane] with
+// k < NV the factored row's entries and k = NV the inverse pivots, handed to noslip (aw_solver.h)
+constexpr int MFAC = (MAXV + 1) * 64;
 #ifdef AW_WIDE
 #define AW_TIER wide
 #else
@@ -265,6 +268,9 @@ constexpr int MAXRG = 64;     // rendered (primitive) geoms
   X(double, geom_size64, MAXG * 3) X(double, cp_margin64, MAXPAIR)                                 \
   X(unsigned long long, cp_kin64, MAXPAIR) /* bodies of the pair's geoms + their ancestors */
 
+// a 16-byte record of four floats (one LDS or global access)
+typedef float MRec __attribute__((ext_vector_type(4)));
+
 struct MData {
 #define AW_X(T, name, n) T name[n];
   AW_MODEL_ARRAYS(AW_X)
@@ -294,6 +300,19 @@ template <class T> using gp_t = __attribute__((address_space(1))) T*;
 template <class T> AW_DEV gp_t<const T> gcp(const T* p) { return (gp_t<const T>)p; }
 template <class T> AW_DEV gp_t<T> gmp(T* p) { return (gp_t<T>)p; }
 #define MDP(name, idx) ::aw::gcp(&m.d->name[idx])
+// per-env I/O (state, actions, params, obs, episode bookkeeping): device-global like the model
+// table, so read and written through global pointers too (AW_IO_GLOBAL; 0 restores generic
+// pointers, whose flat loads also hold lgkmcnt)
+#ifndef AW_IO_GLOBAL
+#define AW_IO_GLOBAL 1
+#endif
+#if AW_IO_GLOBAL
+#define GIN(p) ::aw::gcp(p)
+#define GOUT(p) ::aw::gmp(p)
+#else
+#define GIN(p) (p)
+#define GOUT(p) (p)
+#endif
 
 struct DModel {
   int nq, nv, nu, nbody, njnt, ngeom, nsite, ntendon, npairall, nlevel;
@@ -312,6 +331,7 @@ struct DModel {
   int fault_flrow;            // test hook (aw_set_fault, kind 2): this frictionloss row never slides; -1: off
   const MData* __restrict__ d;
   float* jspill;              // dense-J rows past JL, one block of the tier's JSPILL floats per workgroup slot (device)
+  float* mfac;                // the substep's factor of M, one block of MFAC floats per workgroup slot (device)
   unsigned long long env_offset;   // global id of env 0 of this handle (shards): Philox keys
 };
 

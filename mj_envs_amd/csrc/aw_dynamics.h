@@ -20,7 +20,7 @@ namespace aw {
 // (geom_size: every collider; body_mass: subtree sums); other overrides are applied where
 // the field is read (apply_ovr)
 AW_DEV void stage_model(const DModel& m, Env& s, const float* params, int lane) {
-  if (lane < m.nparam) s.prm[lane] = params ? params[lane] : MD(param_default, lane);
+  if (lane < m.nparam) s.prm[lane] = params ? GIN(params)[lane] : MD(param_default, lane);
   for (int b = lane; b < m.nbody; b += 64) s.bmass[b] = MD(body_mass, b);
   for (int g = lane; g < m.ngeom; g += 64)
     for (int k = 0; k < 3; k++) s.gsize[g][k] = MD(geom_size, 3 * g + k);
@@ -46,6 +46,18 @@ AW_DEV void apply_ovr(const DModel& m, const Env& s, int field, int obj, float (
     }
 }
 
+// AW_JNT_REC (default 1): stage_kinematics first stages one joint per lane -- model record, half
+// angle reduction, v_sin / v_cos, the joint quaternion -- as a 12-float record in the dense-J rows
+// (dead from the end of a forward until its collision stage writes the pair list there), so the
+// per-body joint chain reads LDS records and is left with the frame algebra, as stage_kin64's is.
+// The same expressions on the same values: bitwise the serial form, which 0 restores.
+#ifndef AW_JNT_REC
+#define AW_JNT_REC 1
+#endif
+constexpr int JREC_W = 12;   // {axis, hinge} {anchor, q} {joint quaternion}
+static_assert(MAXV * JREC_W <= JL * VS && (JREC_W * 4) % 16 == 0, "fp32 joint records do not fit in the dense-J rows");
+AW_DEV MRec* jnt_rec32(Env& s, int j) { return reinterpret_cast<MRec*>(&s.J[0][0]) + (JREC_W / 4) * j; }
+
 // mj_kinematics (+ local2global for geoms, sites).  Frames are kept as quaternions only: every
 // position update rotates by the (normalised) quaternion instead of a stored rotation matrix.
 AW_DEV void stage_kinematics(const DModel& m, Env& s, int lane) {
@@ -53,6 +65,24 @@ AW_DEV void stage_kinematics(const DModel& m, Env& s, int lane) {
     s.xpos[0][0] = s.xpos[0][1] = s.xpos[0][2] = 0;
     s.xquat[0][0] = 1; s.xquat[0][1] = s.xquat[0][2] = s.xquat[0][3] = 0;
   }
+#if AW_JNT_REC
+  if (lane < m.njnt) {
+    const int j = lane;
+    float axis[3], jp[3];
+    for (int c = 0; c < 3; c++) { axis[c] = MD(jnt_axis, 3 * j + c); jp[c] = MD(jnt_pos, 3 * j + c); }
+    const bool hinge = MD(jnt_type, j) != JNT_SLIDE;
+    const float q = s.qpos[j];
+    // hardware v_sin / v_cos on the half angle reduced to [-pi, pi]
+    const float hq = hinge ? 0.5f * q : 0.f;
+    const float hr = fmaf(-6.28318530717958648f, rintf(hq * 0.159154943091895336f), hq);
+    const float sn = __sinf(hr), cs = __cosf(hr);
+    const float ql[4] = {cs, axis[0] * sn, axis[1] * sn, axis[2] * sn};
+    MRec* R = jnt_rec32(s, j);
+    R[0] = MRec{axis[0], axis[1], axis[2], hinge ? 1.f : 0.f};
+    R[1] = MRec{jp[0], jp[1], jp[2], q};
+    R[2] = MRec{ql[0], ql[1], ql[2], ql[3]};
+  }
+#endif
   wsync();
   // Body frames without a level sweep.  (A) Lane b composes its body offset and its joints into
   // ONE rigid transform T_b in the parent's frame -- every lane at once, nothing read from another
@@ -75,19 +105,30 @@ AW_DEV void stage_kinematics(const DModel& m, Env& s, int lane) {
       if (k < dn) {
         const int j = da + k;
         float axis[3], jp[3], xa[3], xn[3];
+#if AW_JNT_REC
+        const MRec* R = jnt_rec32(s, j);
+        const MRec ra = R[0], rp = R[1], rq = R[2];
+        for (int c = 0; c < 3; c++) { axis[c] = ra[c]; jp[c] = rp[c]; }
+        const bool hinge = ra[3] != 0.f;
+        const float q = rp[3];
+        const float ql[4] = {rq[0], rq[1], rq[2], rq[3]};
+#else
         for (int c = 0; c < 3; c++) { axis[c] = MD(jnt_axis, 3 * j + c); jp[c] = MD(jnt_pos, 3 * j + c); }
         const bool hinge = MD(jnt_type, j) != JNT_SLIDE;
         const float q = s.qpos[j];
+#endif
         rotvq(xa, axis, tq);
         rotvq(xn, jp, tq);
         add3(xn, xn, tp);
         copy3(s.xaxis[j], xa);    // parent frame; (C) makes them global
         copy3(s.xanchor[j], xn);
+#if !AW_JNT_REC
         // hardware v_sin / v_cos on the half angle reduced to [-pi, pi]
         const float hq = hinge ? 0.5f * q : 0.f;
         const float hr = fmaf(-6.28318530717958648f, rintf(hq * 0.159154943091895336f), hq);
         const float sn = __sinf(hr), cs = __cosf(hr);
         const float ql[4] = {cs, axis[0] * sn, axis[1] * sn, axis[2] * sn};
+#endif
         mulq(tq, tq, ql);
         float v[3];
         rotvq(v, jp, tq);

@@ -158,6 +158,31 @@ AW_DEV void jspill_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// The forward's factor of M (tree_factor's row and inverse pivots, lane = dof) handed to noslip,
+// which inverts the same M: a [k][lane] block per workgroup slot, under the spill rows' rules --
+// vector stores, lane-dependent reload addresses, jspill_fence() between the two.  Default on;
+// -DAW_MFAC_HANDOFF=0 restores noslip's own factor.
+#ifndef AW_MFAC_HANDOFF
+#define AW_MFAC_HANDOFF 1
+#endif
+AW_DEV bool noslip_on(const DModel& m) { return m.noslip_iterations > 0 && !(m.disableflags & DSBL_NOSLIP); }
+template <int NV>
+AW_DEV void mfac_store(const DModel& m, const Env& s, int lane, const float (&row)[NV], float invd) {
+  static_assert((NV + 1) * 64 <= MFAC, "M-factor block");
+  gp_t<float> f = gmp(m.mfac) + (size_t)s.slot * MFAC + lane;
+#pragma unroll
+  for (int k = 0; k < NV; k++) f[64 * k] = row[k];
+  f[64 * NV] = invd;
+}
+template <int NV>
+AW_DEV void mfac_load(const DModel& m, const Env& s, int lane, float (&row)[NV], float& invd) {
+  jspill_fence();
+  gp_t<const float> f = gmp(m.mfac) + (size_t)s.slot * MFAC + lane;
+#pragma unroll
+  for (int k = 0; k < NV; k++) row[k] = f[64 * k];
+  invd = f[64 * NV];
+}
+
 // J_r . x  (x in LDS); r is per lane
 template <int NV>
 AW_DEV float row_dot(const DModel& m, const Env& s, int r, const float* x) {
@@ -919,10 +944,14 @@ AW_DEV void solve_noslip(const DModel& m, Env& s, int lane_ns, const float (&Mro
   float Am[NV];
   {
     float row[NV];
+    float invd;
+#if AW_MFAC_HANDOFF
+    mfac_load<NV>(m, s, lane, row, invd);   // the factor forward() computed for qacc_smooth
+#else
 #pragma unroll
     for (int k = 0; k < NV; k++) row[k] = Mrow[k];
-    float invd;
     tree_factor<TASK>(row, invd, lane);
+#endif
     tree_inverse<TASK>(row, invd, lane, Am);
   }
   if (lane >= NV) {

@@ -3,6 +3,7 @@
 # Deterministic rollouts (tools/rollout_dump.py) of main and of each mj_envs_amd/libadroit_hip_<variant>.so
 # compared array for array, then tools/ab.sh under the random and DAPG policies.  Dumps stay in /tmp
 # on the box (they exceed gpurun_out's size cap); logs go to gpurun_out/TAG_*.
+# ROLLOUT_ENVS="hammer-v0 door-v0 pen-v0 relocate-v0" (environment) dumps those tasks instead of rollout_dump.py's default.
 set -e
 TAG=$1; shift
 timeout -k 10 120 python -u tools/rollout_dump.py /tmp/${TAG}_main.npz > gpurun_out/${TAG}_dump.log 2>&1

@@ -1,8 +1,8 @@
 """Deterministic rollouts for bitwise A/B of library variants (GPU box):
 
-    AW_LIB=... python tools/rollout_dump.py OUT.npz
+    AW_LIB=... python tools/rollout_dump.py OUT.npz [ENV_ID ...]
 
-hammer-v0 / relocate-v0, 4 096 envs: 40 env-steps under random actions and 40 in the DAPG closed loop,
+hammer-v0 / relocate-v0 (or the tasks listed here or in $ROLLOUT_ENVS, e.g. door-v0 pen-v0 as well), 4 096 envs: 40 env-steps under random actions and 40 in the DAPG closed loop,
 with auto-reset; saves the final states and every step's obs.  Two variants whose files are equal
 array for array compute the same arithmetic."""
 import os
@@ -19,7 +19,7 @@ from mj_envs_amd.policy import GaussianMLP  # noqa: E402
 from mj_envs_amd.tasks import attach_task, load_model  # noqa: E402
 
 out = {}
-for env_id in ("hammer-v0", "relocate-v0"):
+for env_id in (sys.argv[2:] or os.environ.get("ROLLOUT_ENVS", "").split() or ("hammer-v0", "relocate-v0")):
     for pol in ("random", "dapg"):
         n = 4096
         sim = _native.Sim(attach_task(load_model(env_id), env_id).to_blob(), n)
