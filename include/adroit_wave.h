@@ -194,6 +194,38 @@ int aw_forward_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, v
 #define AW_CAM_ZFAR 16
 int aw_render_depth(aw_handle* h, const float* cam, int width, int height, float* out, void* stream);
 
+/* RGB camera observation (the frame headless_observer.py:34-52 returns and
+ * CustomPixelObservationWrapper(obs_key="pixels") feeds to PlaNet / the CNN PPO path), from the
+ * same camera record as aw_render_depth.  One launch ray-casts every env's current state into
+ * rgb [N][height][width][3] uint8 and, with depth != NULL (ss must be 1), the aligned depth frame
+ * depth [N][height][width], bit for bit what aw_render_depth writes.
+ *   Opaque pass: the nearest primitive geom (the depth renderer's search), Phong-shaded in linear
+ * [0,1] fp32: c = emission*a + sum over lights [ amb*a + f*(dif*a*max(n.l,0) + [n.l>0]*spe*spec*
+ * max(r.v,0)^(128*shin)) ], a = the geom's rgb (explicit rgba, else its material's; geoms are
+ * opaque), f = attenuation * spot (positional lights with cutoff < 180: (-l.dir)^exponent inside
+ * the cone, 0 outside).  Lights: the camera headlight (a point light at the camera, no cone, no
+ * attenuation), then the model's <light>s (up to 4).  No shadows, reflections, fog, skybox or
+ * textures (a textured material is drawn with its rgba).
+ *   Stand-in rule: the hand's visual geoms are meshes (absent offline); the primitive collision
+ * proxy of a group hidden by default (>= 3) is drawn with the colour and material of the first
+ * mesh geom of its body, if there is one.
+ *   Sites: the visible ones (group 0-2, alpha > 0: hammer nail_goal / S_target, relocate target --
+ * the goal markers) are blended over the opaque colour back to front, c = alpha*shade + (1-alpha)*c,
+ * the 4 nearest crossings in front of the opaque one; they never write depth.  Per-env site_pos
+ * params move them.  Tint rows of the task block (hammer variation "mass": head red = mass / 2.5,
+ * hammer_v0.py:118) replace a colour channel by a scaled per-env param.
+ *   ss in {1, 2}: ss x ss rays at the centres of the pixel's sub-cells, averaged before
+ * floor(255*clamp(c)+0.5).  64x64 with ss = 2 is the box-filtered 128x128 crop (enable_resize).
+ *   look: HOST array of AW_LOOK_FLOATS floats -- background rgb, headlight ambient / diffuse /
+ * specular, headlight active -- or NULL = 0 0 0, 0.1 0.4 0.5, 1.
+ *   Parity: unpinned against the reference (OpenGL, meshes, PNG textures); the kernel is pinned to
+ * the fp64 restatement of this model in tests/rgb_checker.py.
+ * AW_EINVAL: ss not 1 or 2, depth with ss 2, sizes <= 0 or > 1024, NULL rgb.  AW_EUNSUPPORTED: the
+ * model table lacks the appearance arrays (an older file; every other call still works). */
+#define AW_LOOK_FLOATS 7
+int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, int height, int ss,
+                  uint8_t* rgb, float* depth, void* stream);
+
 /* On-device Gaussian MLP policy: mjrl gaussian_mlp.MLP as used by the
  * reference's DAPG baseline (algos/baselines.py:67-86, hidden_sizes=(32, 32)) -- two tanh
  * hidden layers of width `hidden` (32 or 64), in/out affine transforms, and with sample != 0

@@ -98,6 +98,9 @@ def load():
     if hasattr(L, "aw_render_depth"):
         L.aw_render_depth.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]
         L.aw_render_depth.restype = ctypes.c_int
+    if hasattr(L, "aw_render_rgb"):
+        L.aw_render_rgb.argtypes = [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]
+        L.aw_render_rgb.restype = ctypes.c_int
     if hasattr(L, "aw_policy_mlp"):
         L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, _vp]
@@ -115,7 +118,8 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_random_actions", "aw_set_env_offset", "aw_get_state", "aw_set_state", "aw_status",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
-           "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_policy_mlp",
+           "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_render_rgb",
+           "aw_policy_mlp",
            "aw_collide_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
@@ -293,6 +297,28 @@ class Sim:
         c = np.ascontiguousarray(cam, np.float32)
         assert c.size == 17, "render_depth: camera record has 17 floats"
         _check(load().aw_render_depth(self.h, c.ctypes.data, w, h, _ptr(out), _stream()))
+
+    def render_rgb(self, out, cam: np.ndarray, look: Optional[np.ndarray] = None, ss: int = 1, depth=None):
+        """Colour frames of every env's current state into out [N, H, W, 3] (device, uint8) and,
+        with depth [N, H, W] (device, fp32; ss must be 1), the aligned depth frames of the same
+        launch.  cam: the host camera record of mj_envs_amd.render.free_camera; look: 7 host floats
+        (background rgb, headlight ambient / diffuse / specular, headlight on) or None for the
+        defaults (include/adroit_wave.h aw_render_rgb)."""
+        import torch
+        n, h, w, ch = out.shape
+        assert n == self.n_envs and ch == 3 and out.dtype == torch.uint8 and out.is_contiguous(), \
+            "render_rgb: out must be uint8 [n_envs, H, W, 3]"
+        if depth is not None:
+            assert tuple(depth.shape) == (n, h, w) and depth.dtype == torch.float32 and depth.is_contiguous(), \
+                "render_rgb: depth must be fp32 [n_envs, H, W]"
+        c = np.ascontiguousarray(cam, np.float32)
+        assert c.size == 17, "render_rgb: camera record has 17 floats"
+        lk = None
+        if look is not None:
+            lk = np.ascontiguousarray(look, np.float32)
+            assert lk.size == 7, "render_rgb: look record has 7 floats"
+        _check(load().aw_render_rgb(self.h, c.ctypes.data, None if lk is None else lk.ctypes.data, w, h, int(ss),
+                                    _ptr(out), _ptr(depth), _stream()))
 
     def collide_test(self, types, pos, mat, size, margin, fp64: bool = False):
         """narrowphase of n primitive pairs (test hook): list of arrays [(dist, pos[3], normal[3]), ...]

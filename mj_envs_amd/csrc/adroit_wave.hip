@@ -1115,6 +1115,38 @@ __global__ void __launch_bounds__(256) k_depth(DModel m, DState st, int n, CamRe
   for (int p0 = (tid >> 6) * 64; p0 < W * H; p0 += 256) render_span(rg, m.nrgeom, cam.c, W, H, p0, lane, o);
 }
 
+// colour frame (and optionally the aligned depth frame) of every env's current state: k_depth's
+// structure, with the visible sites, the env's colour table and the lights staged next to the
+// geom poses; each wave shades 64-pixel spans (aw_render.h render_span_rgb)
+struct LookRec {
+  float c[AW_LOOK_FLOATS];
+};
+template <int TASK>
+__global__ void __launch_bounds__(256) k_rgb(DModel m, DState st, int n, CamRec cam, LookRec look, int W, int H, int ss,
+                                             unsigned char* out, int dwords, float* depth) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RGeoms rg;
+  __shared__ RColors rc;
+  const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (env >= n) return;
+  if (tid < 64) {
+    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+    wsync();
+    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+    stage_kinematics(m, s, lane);
+  }
+  __syncthreads();
+  render_geoms(m, s, rg, cam.c, tid, 256);
+  render_sites(m, s, rg, cam.c, tid, 256);
+  render_colors(m, s, rc, cam.c, look.c, tid, 256);
+  __syncthreads();
+  unsigned char* o = out + (size_t)env * W * H * 3;
+  float* z = depth ? depth + (size_t)env * W * H : nullptr;
+  for (int p0 = (tid >> 6) * 64; p0 < W * H; p0 += 256)
+    render_span_rgb(rg, rc, m.nrgeom, m.nrsite, cam.c, look.c, W, H, ss, p0, lane, tid >> 6, o, dwords != 0, z);
+}
+
 #ifndef AW_TASK_TU
 __global__ void k_random_actions(int n, int nu, uint64_t seed, uint64_t step, uint64_t env_offset, float* out) {
   int env = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1505,8 +1537,91 @@ static int build_model(const Blob& B, DModel& m, MData& md) {
       rr.push_back(grb[g]);
     }
     m.nrgeom = (int)rt.size();
+    // colour renderer: the visible sites (group 0-2, alpha > 0) follow the geoms, then every
+    // entry's colour record.  A model table without the appearance arrays renders depth only.
+    std::vector<int> rsite(rt.size(), -1);
+    std::vector<float> rcol;
+    m.appearance = B.has("geom_rgba") && B.has("geom_group") && B.has("geom_matid") && B.has("site_rgba") &&
+                   B.has("site_group") && B.has("site_matid") && B.has("site_type") && B.has("site_size") &&
+                   B.has("mat_rgba") && B.has("light_pos");
+    if (m.appearance) {
+      std::vector<double> grgba = B.f("geom_rgba"), srgba = B.f("site_rgba"), mrgba = B.f("mat_rgba"),
+                          mspec = B.f("mat_specular"), mshin = B.f("mat_shininess"), memi = B.f("mat_emission"),
+                          spos = B.f("site_pos"), squat = B.f("site_quat"), ssize = B.f("site_size");
+      std::vector<int> ggroup = B.i("geom_group"), gmat = B.i("geom_matid"), sgroup = B.i("site_group"),
+                       smat = B.i("site_matid"), stype = B.i("site_type"), sbody = B.i("site_bodyid");
+      const int nmat = (int)mspec.size();
+      // rgb: an explicit rgba, else the material's (MuJoCo: a geom rgba left at its default
+      // 0.5 0.5 0.5 1 yields to the material); alpha as written
+      auto record = [&](int src_mat, const double* src_rgba, double alpha) {
+        const bool dflt = src_rgba[0] == 0.5 && src_rgba[1] == 0.5 && src_rgba[2] == 0.5 && src_rgba[3] == 1.0;
+        const double* c = (src_mat >= 0 && dflt) ? &mrgba[4 * src_mat] : src_rgba;
+        for (int k = 0; k < 3; k++) rcol.push_back((float)c[k]);
+        rcol.push_back((float)alpha);
+        rcol.push_back((float)(src_mat >= 0 ? mspec[src_mat] : 0.5));
+        rcol.push_back((float)(128.0 * (src_mat >= 0 ? mshin[src_mat] : 0.5)));
+        rcol.push_back((float)(src_mat >= 0 ? memi[src_mat] : 0.0));
+        rcol.push_back(0.f);
+      };
+      for (int g = 0; g < ngeom_all; g++) {
+        if (gtype[g] == 7) continue;
+        if (gmat[g] >= nmat) return fail(AW_EBLOB, "geom material id out of range");
+        // stand-in rule: a primitive in a group hidden by default (>= 3) is drawn in place of its
+        // body's mesh (absent), with the first mesh geom's colour and material; geoms are opaque
+        int src = g;
+        if (ggroup[g] >= 3)
+          for (int q = 0; q < ngeom_all; q++)
+            if (gtype[q] == 7 && gbody[q] == gbody[g]) { src = q; break; }
+        if (gmat[src] >= nmat) return fail(AW_EBLOB, "geom material id out of range");
+        record(gmat[src], &grgba[4 * src], 1.0);
+      }
+      for (int i = 0; i < nsite; i++) {
+        if (sgroup[i] > 2 || !(srgba[4 * i + 3] > 0)) continue;
+        if (smat[i] >= nmat) return fail(AW_EBLOB, "site material id out of range");
+        rt.push_back(stype[i]); rb.push_back(sbody[i]); rc.push_back(-1); rsite.push_back(i);
+        for (int k = 0; k < 3; k++) { rp.push_back(spos[3 * i + k]); rs.push_back(ssize[3 * i + k]); }
+        for (int k = 0; k < 4; k++) rq.push_back(squat[4 * i + k]);
+        const double* z = &ssize[3 * i];
+        rr.push_back(stype[i] == GEOM_SPHERE ? z[0] : stype[i] == GEOM_CAPSULE ? z[0] + z[1]
+                     : stype[i] == GEOM_CYLINDER ? std::sqrt(z[0] * z[0] + z[1] * z[1])
+                     : stype[i] == GEOM_BOX ? std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]) : 0.0);
+        record(smat[i], &srgba[4 * i], srgba[4 * i + 3]);
+      }
+      m.nrsite = (int)rt.size() - m.nrgeom;
+      if ((int)rt.size() > MAXRG) return fail(AW_EBLOB, "more render entries (primitive geoms + visible sites) than MAXRG");
+      // lights: positional lights with a cutoff below 180 degrees carry cos(cutoff), the others -2
+      std::vector<double> lpos = B.f("light_pos"), ldir = B.f("light_dir"), lamb = B.f("light_ambient"),
+                          ldif = B.f("light_diffuse"), lspe = B.f("light_specular"), latt = B.f("light_attenuation"),
+                          lcut = B.f("light_cutoff"), lexp = B.f("light_exponent");
+      std::vector<int> ldirl = B.i("light_directional");
+      m.nlight = (int)lcut.size();
+      if (m.nlight > MAXLIGHT) return fail(AW_EBLOB, "more lights than MAXLIGHT");
+      std::vector<float> lrec;
+      for (int l = 0; l < m.nlight; l++) {
+        for (const std::vector<double>* v : {&lpos, &ldir, &lamb, &ldif, &lspe, &latt})
+          for (int k = 0; k < 3; k++) lrec.push_back((float)(*v)[3 * l + k]);
+        lrec.push_back(!ldirl[l] && lcut[l] < 180.0 ? (float)std::cos(lcut[l] * 3.14159265358979323846 / 180.0) : -2.f);
+        lrec.push_back((float)lexp[l]);
+        lrec.push_back(ldirl[l] ? 1.f : 0.f);
+        lrec.resize((size_t)(l + 1) * LIGHT_W, 0.f);
+      }
+      PUT(light, lrec);
+      // tint rows of the task block
+      std::vector<int> tint = B.i("task_tint");
+      std::vector<double> tscale = B.f("task_tint_scale");
+      m.ntint = (int)tscale.size();
+      if (m.ntint > MAXTINT || (int)tint.size() != 3 * m.ntint) return fail(AW_EBLOB, "bad tint rows");
+      std::vector<int> te, tc, tsl;
+      for (int t = 0; t < m.ntint; t++) {
+        if (tint[3 * t] < 0 || tint[3 * t] >= (int)rt.size() || tint[3 * t + 1] < 0 || tint[3 * t + 1] > 2 ||
+            tint[3 * t + 2] < 0 || tint[3 * t + 2] >= m.nparam)
+          return fail(AW_EBLOB, "tint row out of range");
+        te.push_back(tint[3 * t]); tc.push_back(tint[3 * t + 1]); tsl.push_back(tint[3 * t + 2]);
+      }
+      PUT(tint_entry, te); PUT(tint_chan, tc); PUT(tint_slot, tsl); PUT(tint_scale, tof(tscale));
+    }
     PUT(rg_type, rt); PUT(rg_body, rb); PUT(rg_cgeom, rc); PUT(rg_pos, rp); PUT(rg_quat, rq);
-    PUT(rg_size, rs); PUT(rg_rbound, rr);
+    PUT(rg_size, rs); PUT(rg_rbound, rr); PUT(rg_site, rsite); PUT(rg_col, rcol);
   }
   {
     // per-object "some parameter overrides this" flags (kinematics applies those overrides inline)
@@ -1648,6 +1763,14 @@ template <int TASK>
 static void launch_depth(aw_handle* h, const CamRec& cam, int W, int H, float* out, hipStream_t st) {
   hipLaunchKernelGGL((k_depth<TASK>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, cam, W, H, out);
 }
+template <int TASK>
+static void launch_rgb(aw_handle* h, const CamRec& cam, const LookRec& look, int W, int H, int ss, uint8_t* rgb,
+                       float* depth, hipStream_t st) {
+  // whole-dword stores need a frame size and a base that are multiples of 4 bytes
+  const int dwords = (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;
+  hipLaunchKernelGGL((k_rgb<TASK>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, cam, look, W, H, ss, rgb,
+                     dwords, depth);
+}
 #endif  // AW_WIDE
 
 // The launchers of one task, behind one table.  Split build: task_ops<TASK> is defined (and with
@@ -1661,12 +1784,13 @@ struct TaskOps {
   void (*set)(aw_handle*, const float*, const float*, const float*, const float*, float*, hipStream_t);
   void (*dump)(aw_handle*, int, const float*, float*, hipStream_t);
   void (*depth)(aw_handle*, const CamRec&, int, int, float*, hipStream_t);
+  void (*rgb)(aw_handle*, const CamRec&, const LookRec&, int, int, int, uint8_t*, float*, hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 #if !defined(AW_API_TU) && !defined(AW_WIDE)
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {step_slots<TASK>, launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
-                              launch_dump<TASK>, launch_depth<TASK>};
+                              launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>};
   return &ops;
 }
 #endif
@@ -2069,6 +2193,24 @@ int aw_render_depth(aw_handle* h, const float* cam, int width, int height, float
   CamRec c;
   memcpy(c.c, cam, sizeof(c.c));   // host array: the camera record travels as a kernel argument
 #define CALL(TT) task_ops<TT>()->depth(h, c, width, height, out, (hipStream_t)stream)
+  DISPATCH_TASK(h->m.task_kind, CALL)
+#undef CALL
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, int height, int ss, uint8_t* rgb,
+                  float* depth, void* stream) {
+  if (!h || !cam || !rgb || width <= 0 || height <= 0 || width > 1024 || height > 1024 || (ss != 1 && ss != 2) ||
+      (depth && ss != 1))
+    return fail(AW_EINVAL, "aw_render_rgb: bad arguments");
+  if (!h->m.appearance) return fail(AW_EUNSUPPORTED, "aw_render_rgb: the model table carries no appearance arrays");
+  HIPCHK(hipSetDevice(h->device));
+  CamRec c;
+  memcpy(c.c, cam, sizeof(c.c));
+  LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
+  if (look) memcpy(l.c, look, sizeof(l.c));
+#define CALL(TT) task_ops<TT>()->rgb(h, c, l, width, height, ss, rgb, depth, (hipStream_t)stream)
   DISPATCH_TASK(h->m.task_kind, CALL)
 #undef CALL
   HIPCHK(hipGetLastError());

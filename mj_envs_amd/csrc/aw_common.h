@@ -210,7 +210,11 @@ enum { ST_BADQPOS = 1, ST_BADQVEL = 2, ST_BADQACC = 4, ST_CON_OVERFLOW = 8, ST_E
 // compiler keep ~100 per-lane 64-bit addresses live across a substep -- spills.)
 constexpr int MAXPAIR = 320;  // explicit pairs + broadphase candidates
 constexpr int MAXTIDX = 16;   // task object ids
-constexpr int MAXRG = 64;     // rendered (primitive) geoms
+constexpr int MAXRG = 64;     // render table: primitive geoms + visible sites (one ballot)
+constexpr int MAXTINT = 4;    // tint rows of the task block
+constexpr int MAXLIGHT = 4;   // model lights (the colour renderer adds the camera headlight)
+constexpr int LIGHT_W = 24;   // light record: pos dir ambient diffuse specular attenuation, cos(cutoff) or -2, exponent, directional
+constexpr int COL_W = 8;      // colour record: rgb alpha specular 128*shininess emission
 
 #define AW_MODEL_ARRAYS(X)                                                                     \
   X(int, body_parentid, MAXB) X(int, body_rootid, MAXB) X(int, body_dofnum, MAXB)               \
@@ -266,7 +270,13 @@ constexpr int MAXRG = 64;     // rendered (primitive) geoms
   X(double, body_pos64, MAXB * 3) X(double, body_quat64, MAXB * 4) X(double, jnt_pos64, MAXV * 3) \
   X(double, jnt_axis64, MAXV * 3) X(double, geom_pos64, MAXG * 3) X(double, geom_quat64, MAXG * 4) \
   X(double, geom_size64, MAXG * 3) X(double, cp_margin64, MAXPAIR)                                 \
-  X(unsigned long long, cp_kin64, MAXPAIR) /* bodies of the pair's geoms + their ancestors */
+  X(unsigned long long, cp_kin64, MAXPAIR) /* bodies of the pair's geoms + their ancestors */ \
+  /* colour renderer (aw_render.h): the render table's entries past nrgeom are the visible sites  \
+     (rg_site: model site id); per entry rgb alpha specular 128*shininess emission; the model's    \
+     lights; tint rows (entry, channel, param slot, scale): a colour read from the env's params */ \
+  X(int, rg_site, MAXRG) X(float, rg_col, MAXRG * COL_W) X(float, light, MAXLIGHT * LIGHT_W)                  \
+  X(int, tint_entry, MAXTINT) X(int, tint_chan, MAXTINT) X(int, tint_slot, MAXTINT)               \
+  X(float, tint_scale, MAXTINT)
 
 // a 16-byte record of four floats (one LDS or global access)
 typedef float MRec __attribute__((ext_vector_type(4)));
@@ -333,6 +343,9 @@ struct DModel {
   float* jspill;              // dense-J rows past JL, one block of the tier's JSPILL floats per workgroup slot (device)
   float* mfac;                // the substep's factor of M, one block of MFAC floats per workgroup slot (device)
   unsigned long long env_offset;   // global id of env 0 of this handle (shards): Philox keys
+  // colour renderer: visible sites after the nrgeom render entries, model lights, tint rows;
+  // appearance 0: the model table carries no colours (an older file) -- depth only
+  int nrsite, nlight, ntint, appearance;
 };
 
 // ---------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
-// aw_render.h -- depth ray casting against primitive geoms (fp32).
+// aw_render.h -- depth and colour ray casting against primitive geoms and sites (fp32).
 //
 // Replaces the reference's OpenGL frame (hand_manipulation_suite/headless_observer.py:34-52)
-// with metric z-depth; see mj_envs_amd/render.py for the camera construction.  numpy
-// restatement for the tests: oracle/depth.py.
+// with metric z-depth and a Phong-shaded colour frame; see mj_envs_amd/render.py for the camera
+// construction and the shading model.  numpy restatements for the tests: oracle/depth.py
+// (geometry), tests/rgb_checker.py (colour).
 #pragma once
 #include "aw_common.h"
 #include "aw_solver.h"
@@ -28,12 +29,34 @@ AW_DEV float ray_prim(const float* pos, const float* mat, const float* size, int
   return ray_geom(pos, mat, size, o, v, type);
 }
 
-// world poses of the rendered geoms of one env (s.xpos / s.xquat from stage_kinematics)
+// world poses of the rendered entries of one env (s.xpos / s.xquat from stage_kinematics):
+// the primitive geoms, then (colour renderer only) the visible sites
 struct RGeoms {
   float pos[MAXRG][3], mat[MAXRG][9], size[MAXRG][3], rb[MAXRG];
   float box[MAXRG][4];   // conservative pixel box of the bounding sphere: col min / max, row min / max
   int type[MAXRG];
 };
+
+// image-space box of entry g's bounding sphere: x / z over the sphere's camera-frame bounding box
+// is extremal at its corners (conservative); behind / straddling the camera or unbounded
+// (planes: rbound 0) -> the whole image
+AW_DEV void pixel_box(RGeoms& r, int g, const float* cam) {
+  const float rb = r.rb[g];
+  float c[3], x = 0.f, y = 0.f, z = 0.f;
+  sub3(c, r.pos[g], cam);
+  x = dot3(c, cam + 9); y = dot3(c, cam + 6); z = dot3(c, cam + 3);
+  float b0 = -1e30f, b1 = 1e30f, b2 = -1e30f, b3 = 1e30f;
+  if (rb > 0.f && z - rb > 1e-3f) {
+    const float z0 = z - rb, z1 = z + rb;
+    const float umin = fminf((x - rb) / z0, (x - rb) / z1), umax = fmaxf((x + rb) / z0, (x + rb) / z1);
+    const float vmin = fminf((y - rb) / z0, (y - rb) / z1), vmax = fmaxf((y + rb) / z0, (y + rb) / z1);
+    b0 = (umin - cam[12]) / cam[13] - 1.f;   // column range (one pixel of slack)
+    b1 = (umax - cam[12]) / cam[13] + 1.f;
+    b2 = (cam[14] - vmax) / cam[15] - 1.f;   // row range
+    b3 = (cam[14] - vmin) / cam[15] + 1.f;
+  }
+  r.box[g][0] = b0; r.box[g][1] = b1; r.box[g][2] = b2; r.box[g][3] = b3;
+}
 
 AW_DEV void render_geoms(const DModel& m, const Env& s, RGeoms& r, const float* cam, int tid, int nthreads) {
   for (int g = tid; g < m.nrgeom; g += nthreads) {
@@ -47,61 +70,246 @@ AW_DEV void render_geoms(const DModel& m, const Env& s, RGeoms& r, const float* 
     mulq(q, bq, lq);
     q2m(r.mat[g], q);
     for (int k = 0; k < 3; k++) r.size[g][k] = cg >= 0 ? s.gsize[cg][k] : MD(rg_size, 3 * g + k);
-    const float rb = MD(rg_rbound, g);
-    r.rb[g] = rb;
+    r.rb[g] = MD(rg_rbound, g);
     r.type[g] = MD(rg_type, g);
-    // image-space box of the bounding sphere: x / z over the sphere's camera-frame bounding box
-    // is extremal at its corners (conservative); behind / straddling the camera or unbounded
-    // (planes: rbound 0) -> the whole image
-    float c[3], x = 0.f, y = 0.f, z = 0.f;
-    sub3(c, r.pos[g], cam);
-    x = dot3(c, cam + 9); y = dot3(c, cam + 6); z = dot3(c, cam + 3);
-    float b0 = -1e30f, b1 = 1e30f, b2 = -1e30f, b3 = 1e30f;
-    if (rb > 0.f && z - rb > 1e-3f) {
-      const float z0 = z - rb, z1 = z + rb;
-      const float umin = fminf((x - rb) / z0, (x - rb) / z1), umax = fmaxf((x + rb) / z0, (x + rb) / z1);
-      const float vmin = fminf((y - rb) / z0, (y - rb) / z1), vmax = fmaxf((y + rb) / z0, (y + rb) / z1);
-      b0 = (umin - cam[12]) / cam[13] - 1.f;   // column range (one pixel of slack)
-      b1 = (umax - cam[12]) / cam[13] + 1.f;
-      b2 = (cam[14] - vmax) / cam[15] - 1.f;   // row range
-      b3 = (cam[14] - vmin) / cam[15] + 1.f;
-    }
-    r.box[g][0] = b0; r.box[g][1] = b1; r.box[g][2] = b2; r.box[g][3] = b3;
+    pixel_box(r, g, cam);
   }
 }
 
-// z-depth of the 64 pixels [p0, p0 + 64) handled by one wave: the geoms whose pixel box meets
-// the rows of this span are found once per wave (lane g tests geom g, ballot), then every lane
-// runs only those: column box, bounding-sphere cull, exact ray-primitive test
-AW_DEV void render_span(const RGeoms& r, int ng, const float* cam, int W, int H, int p0, int lane, float* out) {
-  const int np = W * H;
-  const int p = p0 + lane;
-  const int rlo = p0 / W, rhi = min(p0 + 63, np - 1) / W;
-  const bool on = lane < ng && r.box[lane][2] <= (float)rhi && r.box[lane][3] >= (float)rlo;
-  unsigned long long mask = __ballot(on);
-  const int row = p / W, col = p - row * W;
-  const float u = cam[12] + cam[13] * (float)col, w = cam[14] - cam[15] * (float)row;
-  float d[3];
+// entries [nrgeom, nrgeom + nrsite): the visible sites, at the site positions of stage_kinematics
+// (per-env site_pos overrides applied there)
+AW_DEV void render_sites(const DModel& m, const Env& s, RGeoms& r, const float* cam, int tid, int nthreads) {
+  for (int g = m.nrgeom + tid; g < m.nrgeom + m.nrsite; g += nthreads) {
+    const int b = MD(rg_body, g);
+    float lq[4], bq[4], q[4];
+    for (int k = 0; k < 4; k++) { lq[k] = MD(rg_quat, 4 * g + k); bq[k] = s.xquat[b][k]; }
+    copy3(r.pos[g], s.sxpos[MD(rg_site, g)]);
+    mulq(q, bq, lq);
+    q2m(r.mat[g], q);
+    for (int k = 0; k < 3; k++) r.size[g][k] = MD(rg_size, 3 * g + k);
+    r.rb[g] = MD(rg_rbound, g);
+    r.type[g] = MD(rg_type, g);
+    pixel_box(r, g, cam);
+  }
+}
+
+// the entries among [0, ne) whose pixel box meets the rows of the 64-pixel span at p0: found once
+// per wave (lane g tests entry g, ballot)
+AW_DEV unsigned long long span_entries(const RGeoms& r, int ne, int W, int H, int p0, int lane) {
+  const int rlo = p0 / W, rhi = min(p0 + 63, W * H - 1) / W;
+  const bool on = lane < ne && r.box[lane][2] <= (float)rhi && r.box[lane][3] >= (float)rlo;
+  return __ballot(on);
+}
+
+// unit direction of the ray through image position (col, row) (fractional: supersampling)
+AW_DEV void pixel_ray(const float* cam, float col, float row, float* d) {
+  const float u = cam[12] + cam[13] * col, w = cam[14] - cam[15] * row;
   for (int k = 0; k < 3; k++) d[k] = cam[3 + k] + u * cam[9 + k] + w * cam[6 + k];
   normalize3(d);
-  const float fc = (float)col, fr = (float)row;
+}
+
+// entry g against the ray of pixel (fc, fr): column / row box, bounding-sphere cull against the
+// nearest crossing so far, exact ray-primitive test; the crossing t or -1
+AW_DEV float entry_hit(const RGeoms& r, int g, const float* cam, const float* d, float fc, float fr, float best) {
+  if (fc < r.box[g][0] || fc > r.box[g][1] || fr < r.box[g][2] || fr > r.box[g][3]) return -1.f;
+  const float rb = r.rb[g];
+  if (rb > 0.f) {
+    float oc[3];
+    sub3(oc, r.pos[g], cam);
+    const float tc = dot3(oc, d);
+    const float d2 = dot3(oc, oc) - tc * tc;
+    if (d2 > rb * rb || tc + rb < 0.f || tc - rb > best) return -1.f;
+  }
+  return ray_prim(r.pos[g], r.mat[g], r.size[g], r.type[g], cam, d);
+}
+
+// nearest crossing of the ray with the entries of mask (3e38 if none) and its entry
+AW_DEV float nearest_hit(const RGeoms& r, unsigned long long mask, const float* cam, const float* d, float fc,
+                         float fr, int& hit) {
   float best = 3.0e38f;
+  hit = -1;
   while (mask) {
     const int g = __builtin_ctzll(mask);
     mask &= mask - 1ull;
-    if (fc < r.box[g][0] || fc > r.box[g][1] || fr < r.box[g][2] || fr > r.box[g][3]) continue;
-    const float rb = r.rb[g];
-    if (rb > 0.f) {
-      float oc[3];
-      sub3(oc, r.pos[g], cam);
-      const float tc = dot3(oc, d);
-      const float d2 = dot3(oc, oc) - tc * tc;
-      if (d2 > rb * rb || tc + rb < 0.f || tc - rb > best) continue;
-    }
-    const float t = ray_prim(r.pos[g], r.mat[g], r.size[g], r.type[g], cam, d);
-    if (t >= 0.f && t < best) best = t;
+    const float t = entry_hit(r, g, cam, d, fc, fr, best);
+    if (t >= 0.f && t < best) { best = t; hit = g; }
   }
+  return best;
+}
+
+// z-depth of the 64 pixels [p0, p0 + 64) handled by one wave
+AW_DEV void render_span(const RGeoms& r, int ng, const float* cam, int W, int H, int p0, int lane, float* out) {
+  const int np = W * H;
+  const int p = p0 + lane;
+  const unsigned long long mask = span_entries(r, ng, W, H, p0, lane);
+  const int row = p / W, col = p - row * W;
+  float d[3];
+  pixel_ray(cam, (float)col, (float)row, d);
+  int hit;
+  const float best = nearest_hit(r, mask, cam, d, (float)col, (float)row, hit);
   if (p < np) out[p] = best < 1.0e38f ? best * dot3(d, cam + 3) : cam[16];
+}
+
+// ---------------------------------------------------------------------------------------
+// colour: Phong shading of the nearest opaque geom, visible sites blended over it
+constexpr int MAXSITEHIT = 4;        // translucent crossings kept per ray (the nearest)
+
+struct RColors {
+  float col[MAXRG][COL_W];
+  float light[MAXLIGHT + 1][LIGHT_W];
+  int nlight;
+  unsigned bytes[4][48];             // one wave's 64 rgb pixels, repacked into dwords
+};
+
+// per-env colour table (tint rows: a colour channel read from the env's params) and light list
+// (look: background rgb, headlight ambient / diffuse / specular, headlight on)
+AW_DEV void render_colors(const DModel& m, const Env& s, RColors& c, const float* cam, const float* look, int tid,
+                          int nthreads) {
+  const int ne = m.nrgeom + m.nrsite;
+  for (int i = tid; i < ne * COL_W; i += nthreads) {
+    const int e = i / COL_W, k = i - e * COL_W;
+    float v = MD(rg_col, i);
+    for (int t = 0; t < m.ntint; t++)
+      if (MD(tint_entry, t) == e && MD(tint_chan, t) == k) v = s.prm[MD(tint_slot, t)] * MD(tint_scale, t);
+    c.col[e][k] = v;
+  }
+  const int head = look[6] != 0.f ? 1 : 0;
+  for (int i = tid; i < m.nlight * LIGHT_W; i += nthreads) c.light[head + i / LIGHT_W][i % LIGHT_W] = MD(light, i);
+  if (head && tid == 0) {   // the headlight: a point light at the camera, no cone, no attenuation
+    float* q = c.light[0];
+    for (int k = 0; k < LIGHT_W; k++) q[k] = 0.f;
+    for (int k = 0; k < 3; k++) { q[k] = cam[k]; q[6 + k] = look[3]; q[9 + k] = look[4]; q[12 + k] = look[5]; }
+    q[15] = 1.f;
+    q[18] = -2.f;
+  }
+  if (tid == 0) c.nlight = head + m.nlight;
+}
+
+// outward normal at the point lp of a primitive's surface (entry frame)
+AW_DEV void prim_normal(int type, const float* size, const float* lp, float* n) {
+  n[0] = 0.f; n[1] = 0.f; n[2] = 1.f;                                  // plane
+  if (type == GEOM_SPHERE) copy3(n, lp);
+  else if (type == GEOM_CAPSULE) {                                     // radial from the nearest axis point
+    n[0] = lp[0]; n[1] = lp[1]; n[2] = lp[2] - fminf(fmaxf(lp[2], -size[1]), size[1]);
+  } else if (type == GEOM_CYLINDER) {                                  // the surface the point lies on: side or cap
+    const float side = fabsf(sqrtf(lp[0] * lp[0] + lp[1] * lp[1]) - size[0]), cap = fabsf(fabsf(lp[2]) - size[1]);
+    if (side <= cap) { n[0] = lp[0]; n[1] = lp[1]; n[2] = 0.f; }
+    else n[2] = lp[2];
+  } else if (type == GEOM_BOX) {                                       // the slab the point lies on
+    float e[3];
+    for (int k = 0; k < 3; k++) e[k] = fabsf(fabsf(lp[k]) - size[k]);
+    const int ax = e[0] <= e[1] && e[0] <= e[2] ? 0 : (e[1] <= e[2] ? 1 : 2);
+    for (int k = 0; k < 3; k++) n[k] = k == ax ? lp[k] : 0.f;
+  }
+  normalize3(n);
+}
+
+// x^e for shading exponents: 0 for x <= 0
+AW_DEV float shade_pow(float x, float e) { return x > 0.f ? exp2f(e * log2f(x)) : 0.f; }
+
+// linear rgb of entry g where the ray cam + t d crosses it
+AW_DEV void shade(const RGeoms& r, const RColors& c, int g, const float* cam, const float* d, float t, float* rgb) {
+  float P[3], dif[3], lp[3], nl[3], n[3];
+  for (int k = 0; k < 3; k++) P[k] = cam[k] + t * d[k];
+  sub3(dif, P, r.pos[g]);
+  mulmtv3(lp, r.mat[g], dif);
+  prim_normal(r.type[g], r.size[g], lp, nl);
+  mulmv3(n, r.mat[g], nl);
+  if (dot3(n, d) > 0.f) scl3(n, n, -1.f);              // face the ray origin
+  const float* a = c.col[g];
+  const float spec = a[4], shin = a[5];
+  for (int k = 0; k < 3; k++) rgb[k] = a[6] * a[k];
+  for (int L = 0; L < c.nlight; L++) {
+    const float* q = c.light[L];
+    float l[3], f = 1.f;
+    if (q[20] != 0.f) scl3(l, q + 3, -1.f);
+    else {
+      sub3(l, q, P);
+      const float dist = normalize3(l);
+      f = 1.f / (q[15] + dist * (q[16] + dist * q[17]));
+      if (q[18] > -1.5f) {
+        const float cs = -dot3(l, q + 3);
+        f = cs >= q[18] ? f * shade_pow(cs, q[19]) : 0.f;
+      }
+    }
+    const float ndl = dot3(n, l);
+    float sp = 0.f;
+    if (ndl > 0.f) {
+      float rv = 0.f;
+      for (int k = 0; k < 3; k++) rv -= (2.f * ndl * n[k] - l[k]) * d[k];
+      sp = spec * shade_pow(rv, shin);
+    }
+    const float df = fmaxf(ndl, 0.f);
+    for (int k = 0; k < 3; k++) rgb[k] += q[6 + k] * a[k] + f * (q[9 + k] * a[k] * df + q[12 + k] * sp);
+  }
+}
+
+// colour (and optionally z-depth) of the 64 pixels [p0, p0 + 64) handled by wave `wave`: per
+// sample ray the nearest opaque geom (render_span's search), shaded; the MAXSITEHIT nearest
+// site crossings in front of it blended over it back to front; ss x ss samples averaged
+AW_DEV void render_span_rgb(const RGeoms& r, RColors& c, int ng, int ns, const float* cam, const float* look, int W,
+                            int H, int ss, int p0, int lane, int wave, unsigned char* out, bool dwords,
+                            float* depth) {
+  const int np = W * H;
+  const int p = p0 + lane;
+  const unsigned long long all = span_entries(r, ng + ns, W, H, p0, lane);
+  const unsigned long long gmask = ng < 64 ? all & ((1ull << ng) - 1ull) : all, smask = ng < 64 ? all >> ng : 0ull;
+  const int row = p / W, col = p - row * W;
+  const float fc = (float)col, fr = (float)row;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int sy = 0; sy < ss; sy++)
+    for (int sx = 0; sx < ss; sx++) {
+      // sample at the centre of sub-cell (sx, sy) of the pixel (ss 1: the pixel centre itself)
+      const float ox = ((float)sx + 0.5f) / (float)ss - 0.5f, oy = ((float)sy + 0.5f) / (float)ss - 0.5f;
+      float d[3], rgb[3];
+      pixel_ray(cam, fc + ox, fr + oy, d);
+      int hit;
+      const float best = nearest_hit(r, gmask, cam, d, fc, fr, hit);
+      if (depth && p < np) depth[p] = best < 1.0e38f ? best * dot3(d, cam + 3) : cam[16];
+      if (hit >= 0) shade(r, c, hit, cam, d, best, rgb);
+      else copy3(rgb, look);
+      // the nearest site crossings in front of the opaque one, sorted by t (registers)
+      float st[MAXSITEHIT];
+      int sg[MAXSITEHIT];
+#pragma unroll
+      for (int k = 0; k < MAXSITEHIT; k++) { st[k] = 3.0e38f; sg[k] = -1; }
+      unsigned long long mk = smask;
+      while (mk) {
+        const int g = ng + __builtin_ctzll(mk);
+        mk &= mk - 1ull;
+        float t = entry_hit(r, g, cam, d, fc, fr, best);
+        if (t < 0.f || t >= best) continue;
+        int e = g;
+#pragma unroll
+        for (int k = 0; k < MAXSITEHIT; k++)
+          if (t < st[k]) { const float tt = st[k]; const int gg = sg[k]; st[k] = t; sg[k] = e; t = tt; e = gg; }
+      }
+#pragma unroll
+      for (int k = MAXSITEHIT - 1; k >= 0; k--)
+        if (sg[k] >= 0) {
+          float sc[3];
+          shade(r, c, sg[k], cam, d, st[k], sc);
+          const float al = c.col[sg[k]][3];
+          for (int q = 0; q < 3; q++) rgb[q] = al * sc[q] + (1.f - al) * rgb[q];
+        }
+      for (int q = 0; q < 3; q++) acc[q] += rgb[q];
+    }
+  unsigned char px[3];
+  const float inv = 1.f / (float)(ss * ss);
+  for (int q = 0; q < 3; q++) px[q] = (unsigned char)floorf(255.f * fminf(fmaxf(acc[q] * inv, 0.f), 1.f) + 0.5f);
+  if (!dwords) {
+    if (p < np)
+      for (int q = 0; q < 3; q++) out[(size_t)p * 3 + q] = px[q];
+    return;
+  }
+  // 64 pixels = 192 contiguous bytes: through LDS, then whole dwords from the low lanes (the frame
+  // size and base are multiples of 4 bytes, and so is every span's start, 192 p0 / 64)
+  unsigned char* stage = reinterpret_cast<unsigned char*>(c.bytes[wave]);
+  for (int q = 0; q < 3; q++) stage[3 * lane + q] = px[q];
+  wsync();
+  const int nd = 3 * min(64, np - p0) / 4;
+  if (lane < nd) reinterpret_cast<unsigned*>(out + (size_t)p0 * 3)[lane] = c.bytes[wave][lane];
+  wsync();
 }
 
 }  // namespace aw

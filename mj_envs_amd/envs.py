@@ -135,6 +135,19 @@ class AdroitVecEnv:
         self.sim.render_depth(out, self._cam)
         return out
 
+    def render_rgb(self, width: int = 64, height: int = 64, ss: int = 1, out=None, depth_out=None):
+        """Colour frames [N, height, width, 3] (uint8, device) of every env's current state from
+        the same camera as ``render_depth`` (shading model: mj_envs_amd/render.py); ``ss`` 2
+        averages 2x2 rays per pixel; ``depth_out`` [N, height, width] (fp32, ss 1) receives the
+        aligned depth frames of the same launch."""
+        import torch
+        if getattr(self, "_cam_key", None) != (width, height):
+            self.mj_viewer_headless_setup(width, height, aerial=getattr(self, "_aerial", False))
+        if out is None:
+            out = self.sim.empty(self.num_envs, height, width, 3, dtype=torch.uint8)
+        self.sim.render_rgb(out, self._cam, ss=ss, depth=depth_out)
+        return out
+
     # --- state -----------------------------------------------------------------------------
     def get_state(self) -> Dict[str, "object"]:
         s = self.sim
@@ -285,10 +298,18 @@ class _AdroitEnv(_reference_base()):
     def evaluate_success(self, paths: List[dict]) -> float:
         return _evaluate_success(self.env_id, paths)
 
-    def render(self, *args, **kwargs):
-        """Depth frame [height, width] (float64, metres) of the current state.  The reference
-        returns an RGB frame from OpenGL (headless_observer.py:34-52); RGB is not rendered here,
-        the HIP ray caster produces metric depth from the same camera (mj_envs_amd/render.py)."""
+    def render(self, *args, mode: str = "depth", enable_resize: bool = True, **kwargs):
+        """Default: the depth frame [height, width] (float64, metres) of the current state.
+        ``mode="rgb"``: the colour frame ``HeadlessObserver.render`` returns
+        (headless_observer.py:34-52), float64 [H, W, 3] in 0..255 from the HIP ray caster's shading
+        model (mj_envs_amd/render.py; parity-unpinned against the reference's OpenGL frame):
+        64x64 with 2x2 rays per pixel when ``enable_resize`` (the reference's resized 128x128 crop),
+        else the 128x128 crop itself."""
+        if mode == "rgb":
+            size, ss = (64, 2) if enable_resize else (128, 1)
+            return self.vec.render_rgb(size, size, ss=ss)[0].cpu().numpy().astype(np.float64)
+        if mode != "depth":
+            raise ValueError(f"render: mode must be 'depth' or 'rgb', not {mode!r}")
         return self.vec.render_depth(self.width, self.height)[0].cpu().numpy().astype(np.float64)
 
     # pen's flag (pen_v0.py:23, read by its mj_viewer_headless_setup, :174-177)

@@ -47,6 +47,15 @@ SENS_TYPES = {"touch": 0, "jointpos": 1, "actuatorfrc": 2}
 MJ_MINVAL = 1e-15
 DEFAULT_SOLREF = [0.02, 1.0]
 DEFAULT_SOLIMP = [0.9, 0.95, 0.001, 0.5, 2.0]
+DEFAULT_RGBA = [0.5, 0.5, 0.5, 1.0]      # geom / site rgba when the XML gives none
+
+# appearance of a model (colour renderer): kept in a file of its own (Model.save_npz)
+APPEARANCE_ARRAYS = ("geom_rgba", "geom_group", "geom_matid", "site_rgba", "site_group", "site_matid",
+                     "mat_rgba", "mat_specular", "mat_shininess", "mat_emission", "light_pos", "light_dir",
+                     "light_directional", "light_ambient", "light_diffuse", "light_specular",
+                     "light_attenuation", "light_cutoff", "light_exponent")
+APPEARANCE_DIMS = ("nmat", "nlight")
+APPEARANCE_NAMES = ("material",)
 
 BLOB_MAGIC = b"AWMB"
 BLOB_VERSION = 1
@@ -231,16 +240,20 @@ class Model:
             out.append(np.ascontiguousarray(a).tobytes())
         return b"".join(out)
 
-    def save_npz(self, path: str):
-        payload = {"a_" + k: v for k, v in self.arrays.items()}
-        payload.update({"d_" + k: np.array(v) for k, v in self.dims.items()})
-        payload.update({"o_" + k: np.array(v) for k, v in self.opt.items()})
-        payload.update({"n_" + k: np.array(v, dtype="U64") for k, v in self.names.items()})
+    def save_npz(self, path: str, appearance: bool = False):
+        """The model without its appearance part (``APPEARANCE_*``), or with ``appearance`` that
+        part alone: two files, read back with ``load_npz`` and ``load_npz(into=model)``."""
+        pick = lambda d, keys: {k: v for k, v in d.items() if (k in keys) == appearance}
+        payload = {"a_" + k: v for k, v in pick(self.arrays, APPEARANCE_ARRAYS).items()}
+        payload.update({"d_" + k: np.array(v) for k, v in pick(self.dims, APPEARANCE_DIMS).items()})
+        if not appearance:
+            payload.update({"o_" + k: np.array(v) for k, v in self.opt.items()})
+        payload.update({"n_" + k: np.array(v, dtype="U64") for k, v in pick(self.names, APPEARANCE_NAMES).items()})
         np.savez_compressed(path, **payload)
 
     @classmethod
-    def load_npz(cls, path: str) -> "Model":
-        m = cls()
+    def load_npz(cls, path: str, into: Optional["Model"] = None) -> "Model":
+        m = cls() if into is None else into
         with np.load(path, allow_pickle=False) as z:
             for k in z.files:
                 v = z[k]
@@ -279,7 +292,7 @@ class _Compiler:
                 raise NotImplementedError("only angle='radian' is used by the Adroit models")
             self.eulerseq = c.get("eulerseq", self.eulerseq)
 
-        self.bodies, self.joints, self.geoms, self.sites = [], [], [], []
+        self.bodies, self.joints, self.geoms, self.sites, self.lights = [], [], [], [], []
         world = dict(name="world", parent=-1, pos=np.zeros(3), quat=np.array([1.0, 0, 0, 0]),
                      mass=0.0, ipos=np.zeros(3), iquat=np.array([1.0, 0, 0, 0]),
                      inertia=np.zeros(3), mocap=False, joints=[], geoms=[], sites=[], cameras=[],
@@ -329,6 +342,10 @@ class _Compiler:
             elif tag == "site":
                 a = self.defaults.attrs("site", child, cls)
                 body["sites"].append(a)
+            elif tag == "light":
+                if bid != 0:
+                    raise NotImplementedError("lights outside the worldbody are not used by the Adroit models")
+                self.lights.append(dict(child.attrib))
             elif tag == "camera":
                 # position only: the render camera needs cam_xpos (headless_observer.py:59-66)
                 body["cameras"].append(np.array(_floats(child.get("pos", "0 0 0"))))
@@ -524,6 +541,33 @@ class _Compiler:
         site_quat = np.array([self._orient(a) for _, a in sites]).reshape(nsite, 4)
         site_names = [a.get("name", "") for _, a in sites]
 
+        # appearance (colour renderer): materials, per geom / site rgba, group and material id,
+        # lights.  MuJoCo's documented defaults where the XML is silent (XML reference: geom / site
+        # rgba "0.5 0.5 0.5 1", material rgba "1 1 1 1" specular 0.5 shininess 0.5 emission 0,
+        # light ambient 0 diffuse 0.7 specular 0.3 attenuation "1 0 0" cutoff 45 exponent 10
+        # dir "0 0 -1").  The material's texture attribute is ignored (textures are not rendered).
+        mats = [dict(e.attrib) for asec in self.root.findall("asset") for e in asec if e.tag == "material"]
+        mat_names = [a.get("name", "") for a in mats]
+        nmat = len(mats)
+
+        def _appearance(objs):
+            rgba = np.array([(_floats(a["rgba"]) if "rgba" in a else DEFAULT_RGBA) for _, a in objs])
+            group = np.array([int(a.get("group", "0")) for _, a in objs], np.int32)
+            matid = np.array([mat_names.index(a["material"]) if "material" in a else -1 for _, a in objs],
+                             np.int32)
+            return rgba.reshape(len(objs), 4), group, matid
+
+        geom_rgba, geom_group, geom_matid = _appearance(geoms)
+        site_rgba, site_group, site_matid = _appearance(sites)
+
+        def _rgb(a, key, dflt):
+            v = _floats(a[key]) if key in a else [dflt]
+            return v * 3 if len(v) == 1 else v[:3]
+
+        nlight = len(self.lights)
+        light_dir = np.array([_floats(a.get("dir", "0 0 -1")) for a in self.lights]).reshape(nlight, 3)
+        light_dir = light_dir / np.maximum(np.linalg.norm(light_dir, axis=1, keepdims=True), MJ_MINVAL)
+
         # tendons (fixed)
         ten_limited, ten_range, ten_margin, ten_solref, ten_solimp, ten_floss = [], [], [], [], [], []
         ten_adr, ten_num, wrap_jnt, wrap_coef, ten_names = [], [], [], [], []
@@ -673,6 +717,21 @@ class _Compiler:
         A["site_size"] = site_size
         A["site_pos"] = site_pos
         A["site_quat"] = site_quat
+        A["geom_rgba"], A["geom_group"], A["geom_matid"] = geom_rgba, geom_group, geom_matid
+        A["site_rgba"], A["site_group"], A["site_matid"] = site_rgba, site_group, site_matid
+        A["mat_rgba"] = np.array([_floats(a.get("rgba", "1 1 1 1")) for a in mats]).reshape(nmat, 4)
+        A["mat_specular"] = np.array([float(a.get("specular", "0.5")) for a in mats])
+        A["mat_shininess"] = np.array([float(a.get("shininess", "0.5")) for a in mats])
+        A["mat_emission"] = np.array([float(a.get("emission", "0")) for a in mats])
+        A["light_pos"] = np.array([_floats(a.get("pos", "0 0 0")) for a in self.lights]).reshape(nlight, 3)
+        A["light_dir"] = light_dir
+        A["light_directional"] = np.array([a.get("directional", "false") == "true" for a in self.lights], np.int32)
+        A["light_ambient"] = np.array([_rgb(a, "ambient", 0.0) for a in self.lights]).reshape(nlight, 3)
+        A["light_diffuse"] = np.array([_rgb(a, "diffuse", 0.7) for a in self.lights]).reshape(nlight, 3)
+        A["light_specular"] = np.array([_rgb(a, "specular", 0.3) for a in self.lights]).reshape(nlight, 3)
+        A["light_attenuation"] = np.array([_floats(a.get("attenuation", "1 0 0")) for a in self.lights]).reshape(nlight, 3)
+        A["light_cutoff"] = np.array([float(a.get("cutoff", "45")) for a in self.lights])
+        A["light_exponent"] = np.array([float(a.get("exponent", "10")) for a in self.lights])
         cams = [(bi, c) for bi, b in enumerate(B) for c in b.get("cameras", [])]
         A["cam_bodyid"] = np.array([bi for bi, _ in cams], np.int32)
         A["cam_pos"] = np.array([c for _, c in cams], np.float64).reshape(len(cams), 3)
@@ -708,10 +767,10 @@ class _Compiler:
         A["qpos0"] = np.zeros(nq)
 
         m.names = dict(body=body_names, joint=jnt_names, geom=geom_names, site=site_names,
-                       tendon=ten_names, actuator=act_names, sensor=sens_names)
+                       tendon=ten_names, actuator=act_names, sensor=sens_names, material=mat_names)
         m.dims = dict(nq=nq, nv=nv, nu=nu, nbody=nbody, njnt=njnt, ngeom=ngeom, nsite=nsite,
                       ntendon=ntendon, nwrap=len(wrap_jnt), nsensor=nsensor, nsensordata=nsensor,
-                      npair=npair, nexclude=len(excludes))
+                      npair=npair, nexclude=len(excludes), nmat=nmat, nlight=nlight)
         m.opt = dict(timestep=self.opt["timestep"], gravity_x=self.opt["gravity"][0],
                      gravity_y=self.opt["gravity"][1], gravity_z=self.opt["gravity"][2],
                      iterations=self.opt["iterations"], tolerance=self.opt["tolerance"],

@@ -1,4 +1,4 @@
-"""Depth-camera observations (BASELINE config 5).
+"""Camera observations: depth and colour (BASELINE config 5).
 
 The reference renders RGB through OpenGL from mujoco-py's offscreen free camera
 (``hand_manipulation_suite/headless_observer.py:20-52``):
@@ -19,6 +19,28 @@ meets those rows and casts its rays against only those.  The output is metric z-
 counterpart (the reference returns RGB), so this path is parity-unpinned against the
 reference; it is checked against an independent numpy ray caster on the fp64 oracle's
 kinematics (``oracle/depth.py``, ``tests/test_render.py``).
+
+Colour (``aw_render_rgb``, ``k_rgb``) comes from the same camera record, unchanged: per sample
+ray the depth renderer's nearest opaque geom, shaded in linear [0, 1] fp32 with
+
+    c = emission a + sum_L [ amb_L a + f_L ( dif_L a max(n.l, 0) + [n.l > 0] spe_L spec max(r.v, 0)^(128 shin) ) ]
+
+(a: the geom's rgb -- an explicit rgba, else its material's; n: the surface normal facing the ray;
+l: towards the light, r = reflect(-l, n), v = -ray; f_L = attenuation x spot cone), under the
+camera headlight (a point light at the camera: ambient 0.1, diffuse 0.4, specular 0.5) followed
+by the model's lights; then the visible sites (group 0-2, alpha > 0: the goal markers -- hammer's
+``nail_goal`` / ``S_target``, relocate's per-env ``target``) blended over it back to front,
+``c = alpha shade + (1 - alpha) c``.  With ``ss = 2`` four rays through the centres of the pixel's
+sub-cells are averaged, so the 64x64 frame is the box-filtered 128x128 crop (the reference's
+``enable_resize`` frame); the result is quantised ``floor(255 clamp(c) + 0.5)`` to uint8
+``[N, H, W, 3]``, optionally with the aligned depth frame of the same launch (RGB-D).
+Stand-in rule: a collision proxy in a group hidden by default (>= 3) is drawn in the colour and
+material of the first mesh geom of its body (the hand: ``MatViz``); geoms are opaque.  Tint rows
+of the task block show a per-env param as a colour: hammer's ``variation_type="mass"`` sets the
+head's red channel to ``mass / 2.5`` as the reference does (``hammer_v0.py:118``).  No textures
+(a textured material is drawn with its rgba), shadows, reflections, fog or skybox.  Like depth
+this is parity-unpinned against the reference's OpenGL frame; it is checked against an fp64 numpy
+restatement of the model above (``tests/rgb_checker.py``, ``tests/test_render_rgb.py``).
 
 Reference quirks kept: hammer sets up its observer once, in ``__init__``, while ``obj_bid`` is
 still the placeholder ``-1`` (``hammer_v0.py:15,35-38``), so the elevation uses the LAST body.

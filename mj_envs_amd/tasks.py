@@ -54,16 +54,27 @@ TASKS: Dict[str, TaskSpec] = {
 }
 
 MODEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
+# the models' appearance part (colours, materials, lights: mjcf.APPEARANCE_*), one file per model
+APPEARANCE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+
+
+def appearance_path(xml: str) -> str:
+    return os.path.join(APPEARANCE_DIR, "appearance_" + xml.replace(".xml", ".npz"))
 
 
 def load_model(env_id: str):
-    """Compiled model for ``env_id`` (committed ``models/*.npz``, built by tools/compile_assets.py)."""
+    """Compiled model for ``env_id`` (committed ``models/*.npz`` plus its appearance part,
+    ``tests/golden/appearance_*.npz``; both built by tools/compile_assets.py).  Without the
+    appearance file the model still simulates and renders depth; only colour is unavailable."""
     from .mjcf import Model
     spec = TASKS[env_id]
     path = os.path.join(MODEL_DIR, spec.xml.replace(".xml", ".npz"))
     if not os.path.exists(path):
         raise FileNotFoundError(f"compiled model {path} missing; run tools/compile_assets.py")
-    return Model.load_npz(path)
+    m = Model.load_npz(path)
+    if os.path.exists(appearance_path(spec.xml)):
+        Model.load_npz(appearance_path(spec.xml), into=m)
+    return m
 
 
 # ---------------------------------------------------------------------------------------
@@ -228,6 +239,24 @@ def pen_lengths(model) -> Tuple[float, float]:
     return float(np.linalg.norm(a)), float(np.linalg.norm(b))
 
 
+def render_entry(model, geom: int) -> int:
+    """Index of a primitive geom in the render table (the non-mesh geoms in model order)."""
+    assert model.geom_type[geom] != 7, "mesh geoms are not rendered"
+    return int(np.sum(np.asarray(model.geom_type[:geom]) != 7))
+
+
+def tint_rows(env_id: str, model, variation_type: Optional[str] = None) -> List[Tuple[int, int, int, float]]:
+    """(render entry, colour channel, param slot, scale): colours the colour renderer takes from
+    the env's params.  The reference shows hammer's drawn mass in the head's red channel:
+    ``geom_rgba[head, 0] = mass / 2.5`` (``hammer_v0.py:118``); no other task or variation
+    writes a colour."""
+    if env_id == "hammer-v0" and variation_type == "mass":
+        lay = param_layout(env_id, model, variation_type)
+        slot = lay.index(("body_mass", model.name2id("body", "Object"), 0))
+        return [(render_entry(model, model.name2id("geom", "head")), 0, slot, 1.0 / 2.5)]
+    return []
+
+
 def attach_task(model, env_id: str, variation_type: Optional[str] = None):
     """Add the task block (kind, indices, params layout, frame skip ...) to a model copy."""
     import copy
@@ -250,6 +279,9 @@ def attach_task(model, env_id: str, variation_type: Optional[str] = None):
     m.dims.update(task_kind=spec.kind, task_frame_skip=spec.frame_skip, task_horizon=spec.horizon,
                   task_obs_dim=spec.obs_dim, task_nparam=len(lay), task_variation=var,
                   task_success_steps=spec.success_steps)
+    tint = tint_rows(env_id, model, variation_type)
+    m.arrays["task_tint"] = np.array([t[:3] for t in tint], np.int32).reshape(len(tint), 3)
+    m.arrays["task_tint_scale"] = np.array([t[3] for t in tint], np.float64)
     if env_id == "pen-v0":
         pl, tl = pen_lengths(model)
         m.opt.update(task_pen_length=pl, task_tar_length=tl)

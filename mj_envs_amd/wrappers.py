@@ -7,8 +7,12 @@
   info)`` (gym 0.26 ``StepAPICompatibility``, ``:34``); an ``action_repeat`` loop with the
   wrapper's ``timer`` and ``max_episode_length`` 200 (``:38-40,57-68``).
   Pixels: the reference renders a 64x64 RGB frame through OpenGL every step; here a pixel
-  observation is the HIP ray caster's 64x64 metric depth frame ``[N, 1, H, W]`` from the same
-  camera (``mj_envs_amd/render.py``), rendered only when pixels are asked for.
+  observation comes from the HIP ray caster, from the same camera (``mj_envs_amd/render.py``),
+  rendered only when pixels are asked for: by default the 64x64 metric depth frame
+  ``[N, 1, H, W]``; with ``render_kwargs={"mode": "rgb", "ss": 2}`` the colour frame
+  ``[N, H, W, 3]`` float32 in 0..255 (Phong-shaded primitives, the hand's collision proxies in
+  its mesh material's colour, the goal-marker sites blended in; parity-unpinned against the
+  reference's OpenGL frame).
 * ``SB3VecEnv`` -- the stable-baselines3 ``VecEnv`` method surface (``reset``, ``step_async`` /
   ``step_wait``, ``step``, ``get_attr`` / ``set_attr`` / ``env_method``, ``env_is_wrapped``,
   ``seed``, ``close``, ``num_envs``, spaces) without importing SB3; numpy out as SB3 expects
@@ -59,6 +63,9 @@ class PixelObservationVecEnv:
         self.num_envs = env.num_envs
         self.obs_key = obs_key
         self.width, self.height = int(rk.get("width", 64)), int(rk.get("height", 64))
+        self.mode, self.ss = rk.get("mode", "depth"), int(rk.get("ss", 1))
+        if self.mode not in ("depth", "rgb"):
+            raise ValueError(f"render_kwargs['mode'] must be 'depth' or 'rgb', not {self.mode!r}")
         self.action_repeat = int(action_repeat)
         self.max_episode_length = 200          # wrappers.py:39 (hard-coded there too)
         import torch
@@ -67,7 +74,8 @@ class PixelObservationVecEnv:
         self._pixels_fresh = False
         self.action_space = env.action_space
         self.state_space = env.observation_space
-        self.pixel_space = Box(0.0, np.inf, (1, self.height, self.width))
+        self.pixel_space = Box(0.0, 255.0, (self.height, self.width, 3)) if self.mode == "rgb" \
+            else Box(0.0, np.inf, (1, self.height, self.width))
         self.observation_space = self.pixel_space if obs_key == PIXELS_KEY else self.state_space
 
     # --- observations --------------------------------------------------------------------
@@ -79,10 +87,18 @@ class PixelObservationVecEnv:
 
     def get_pixels(self):
         if not self._pixels_fresh:
-            if self._pixels is None:
-                self._pixels = self.env.sim.empty(self.num_envs, 1, self.height, self.width)
-            self.env.render_depth(self.width, self.height, out=self._pixels.view(self.num_envs, self.height,
-                                                                                 self.width))
+            n, h, w = self.num_envs, self.height, self.width
+            if self.mode == "rgb":
+                if self._pixels is None:
+                    import torch
+                    self._rgb8 = self.env.sim.empty(n, h, w, 3, dtype=torch.uint8)   # what the kernel writes
+                    self._pixels = self.env.sim.empty(n, h, w, 3)
+                self.env.render_rgb(w, h, ss=self.ss, out=self._rgb8)
+                self._pixels.copy_(self._rgb8)                                       # float32 0..255
+            else:
+                if self._pixels is None:
+                    self._pixels = self.env.sim.empty(n, 1, h, w)
+                self.env.render_depth(w, h, out=self._pixels.view(n, h, w))
             self._pixels_fresh = True
         return self._out(self._pixels)
 
@@ -217,11 +233,18 @@ class SB3VecEnv:
 def make_env(config, num_envs: int = 1, device: int = 0):
     """``utils/helpers.py:56-78`` make_env for the Adroit suite, batched: ``config.env_name``,
     ``config.variation_type``, ``config.state_type`` ('observation' -> pixels, 'vector' ->
-    state), ``config.nogui`` (False: the GUI wrapper, state tensors, no pixels)."""
+    state), ``config.nogui`` (False: the GUI wrapper, state tensors, no pixels); optional
+    ``config.pixel_mode``: ``"depth"`` (default) or ``"rgb"`` (colour pixels, 2x2 rays per pixel:
+    the reference's resized frame)."""
     env = AdroitVecEnv(config.env_name, num_envs, device=device,
                        variation_type=getattr(config, "variation_type", None),
                        seed=int(getattr(config, "seed", 1) or 1))
     rk = dict(width=64, height=64)
+    mode = getattr(config, "pixel_mode", "depth") or "depth"
+    if mode == "rgb":
+        rk.update(mode="rgb", ss=2)
+    elif mode != "depth":
+        raise Exception(f"Unsupported pixel mode '{mode}'")
     if not getattr(config, "nogui", True):
         return PixelObservationVecEnv(env, obs_key=STATE_KEY, render_kwargs=rk)
     st = getattr(config, "state_type", "vector")

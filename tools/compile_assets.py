@@ -1,4 +1,5 @@
-"""Compile the reference's Adroit MJCF into the committed model tables (models/*.npz).
+"""Compile the reference's Adroit MJCF into the committed model tables (models/*.npz) and
+their appearance parts (tests/golden/appearance_*.npz).
 
 Run in the build container (where /root/reference exists):
     python tools/compile_assets.py [--assets DIR]
@@ -10,7 +11,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mj_envs_amd.mjcf import compile_mjcf  # noqa: E402
-from mj_envs_amd.tasks import MODEL_DIR, TASKS  # noqa: E402
+from mj_envs_amd.tasks import APPEARANCE_DIR, MODEL_DIR, TASKS, appearance_path  # noqa: E402
 
 DEFAULT_ASSETS = "/root/reference/mj_envs_vision/hand_manipulation_suite/assets"
 
@@ -24,7 +25,9 @@ def main():
         m = compile_mjcf(os.path.join(args.assets, spec.xml))
         out = os.path.join(MODEL_DIR, spec.xml.replace(".xml", ".npz"))
         m.save_npz(out)
-        print(spec.env_id, m.dims, "->", out)
+        os.makedirs(APPEARANCE_DIR, exist_ok=True)
+        m.save_npz(appearance_path(spec.xml), appearance=True)     # colours, materials, lights
+        print(spec.env_id, m.dims, "->", out, appearance_path(spec.xml))
 
 
 if __name__ == "__main__":

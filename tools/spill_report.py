@@ -1,4 +1,5 @@
-"""Attribute scratch (spill) instructions of k_step<TASK> to source lines (debug .s build)."""
+"""Attribute scratch (spill) instructions of k_step<TASK> to source lines (debug .s build).
+AW_SPILL_KERNEL=k_rgb (or another kernel template's name) reports that kernel instead."""
 import collections, re, subprocess, sys
 task = sys.argv[1] if len(sys.argv) > 1 else "0"   # task kind (hammer 0)
 src = "mj_envs_amd/csrc/adroit_wave.hip"
@@ -14,7 +15,8 @@ fmap = {}
 for l in lines:
     m = re.match(r'\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]+)"', l)
     if m: fmap[m.group(1)] = m.group(2)
-s = next(i for i, l in enumerate(lines) if l.startswith(f"_Z6k_stepILi{task}"))
+kernel = os.environ.get("AW_SPILL_KERNEL", "k_step")
+s = next(i for i, l in enumerate(lines) if l.startswith(f"_Z{len(kernel)}{kernel}ILi{task}"))
 e = next(i for i in range(s + 1, len(lines)) if lines[i].startswith(".Lfunc_end"))
 cur = None; cnt = collections.Counter(); n = 0
 for l in lines[s:e]:
@@ -24,6 +26,6 @@ for l in lines[s:e]:
     if not t or t.startswith((".", ";")) or t.endswith(":"): continue
     n += 1
     if "scratch_" in t: cnt[cur] += 1
-print("k_step instructions", n, "scratch ops", sum(cnt.values()))
+print(kernel, "instructions", n, "scratch ops", sum(cnt.values()))
 for k, c in cnt.most_common(25): print(c, k)
 print([l.strip() for l in lines[e:e+400] if "vgpr_count" in l or "private_segment" in l or "vgpr_spill" in l][:6])
