@@ -100,6 +100,23 @@ int aw_set_tier(aw_handle* h, int mode);
  * row never enters a linear zone and noslip never lets it slide).  Waits for the device. */
 int aw_set_fault(aw_handle* h, int kind, int arg);
 
+/* MuJoCo's sensordata (sim.data.sensordata of the reference after step() / reset() /
+ * set_env_state()): every sensor of the model in its declared order -- the Adroit models carry
+ * actuatorfrc, touch and jointpos sensors (DAPG_assets.xml:269-342), one scalar each, 65 in all
+ * (hammer 66 with S_nail).  Off by default: aw_set_sensors(h, 1) allocates the [N][nsensordata]
+ * buffer (zero until an env's next step, reset or set_state) and selects the instantiation of the
+ * step kernels that also evaluates the sensors; with sensors off the step is the kernel it was.
+ * Values are those of the last mj_forward before the last integration of the env-step (the lag the
+ * observation has): jointpos = qpos there, actuatorfrc = the actuator's scalar force after the
+ * forcerange clamp, touch = mj_sensorAcc's sum of the positive contact normal forces on the site's
+ * body whose normal ray meets the site's volume.  An env that auto-reset in a step holds its reset
+ * forward's values, aligned with obs.  mjDSBL_SENSOR zeroes every entry.  aw_set_sensors waits for
+ * the device; aw_sensordata copies the buffer to out (device [N][nsensordata], fp32) and is
+ * AW_EINVAL while sensors are disabled. */
+int aw_set_sensors(aw_handle* h, int enable);
+int aw_sensor_count(const aw_handle* h);
+int aw_sensordata(aw_handle* h, float* out, void* stream);
+
 /* Reset envs (mask[e] != 0, or all if mask == NULL): qpos = qpos0, qvel = 0, warmstart = 0,
  * per-env model params from `params` [N][nparam] or, if NULL, sampled on device (Philox,
  * keyed by seed, global env id and episode count) from the reference reset distribution;

@@ -71,6 +71,12 @@ def load():
     L.aw_random_actions.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]
     L.aw_set_env_offset.argtypes = [_vp, ctypes.c_uint64]
     L.aw_set_tier.argtypes = [_vp, ctypes.c_int]
+    if hasattr(L, "aw_set_sensors"):
+        L.aw_set_sensors.argtypes = [_vp, ctypes.c_int]
+        L.aw_sensor_count.argtypes = [_vp]
+        L.aw_sensordata.argtypes = [_vp, _vp, _vp]
+        for f in ("aw_set_sensors", "aw_sensor_count", "aw_sensordata"):
+            getattr(L, f).restype = ctypes.c_int
     if hasattr(L, "aw_forward_dump_wide"):
         L.aw_forward_dump_wide.argtypes = [_vp, ctypes.c_int, _vp, _vp, _vp]
         L.aw_forward_dump_wide.restype = ctypes.c_int
@@ -115,6 +121,7 @@ def load():
 
 
 EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier", "aw_set_fault", "aw_reset", "aw_step",
+           "aw_set_sensors", "aw_sensor_count", "aw_sensordata",
            "aw_random_actions", "aw_set_env_offset", "aw_get_state", "aw_set_state", "aw_status",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
@@ -203,6 +210,8 @@ class Sim:
          self.task_kind, self.n_envs, self.nbody, self.nsite, self.ngeom, self.npair,
          self.maxcon, self.maxefc, self.maxdense, self.grid, self.fast_maxcon, self.fast_maxefc,
          self.fast_maxdense, self.wide_grid) = list(d)
+        # the model's sensordata length (65 / 66); 0 with an older diagnostic library (AW_LIB)
+        self.nsensordata = int(L.aw_sensor_count(self.h)) if hasattr(L, "aw_sensor_count") else 0
         self.env_offset = 0
         if env_offset:
             self.set_env_offset(env_offset)
@@ -234,6 +243,21 @@ class Sim:
     def set_tier(self, mode: int):
         """0: automatic (fast tier, wide tier for overflowing env-steps); 1: wide tier only (tests)"""
         _check(load().aw_set_tier(self.h, int(mode)))
+
+    def set_sensors(self, enable: bool):
+        """MuJoCo's sensordata on or off (off at create): on, every step / reset / set_state also
+        evaluates the model's sensors into a device buffer [n_envs, nsensordata], read with
+        ``sensordata`` (include/adroit_wave.h aw_set_sensors); off, the step is the kernel it was"""
+        _check(load().aw_set_sensors(self.h, int(bool(enable))))
+
+    def sensordata(self, out):
+        """copy the sensor buffer into out [n_envs, nsensordata] (device, fp32); raises while
+        sensors are off"""
+        import torch
+        assert tuple(out.shape) == (self.n_envs, self.nsensordata) and out.dtype == torch.float32 and \
+            out.is_contiguous(), "sensordata: out must be fp32 [n_envs, nsensordata]"
+        _check(load().aw_sensordata(self.h, _ptr(out), _stream()))
+        return out
 
     def set_fault(self, kind: int, arg: int = 0):
         """test hook (include/adroit_wave.h aw_set_fault): 0 none, 1 class-1 margins + arg um,

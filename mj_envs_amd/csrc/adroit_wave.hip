@@ -553,7 +553,10 @@ AW_DEV void park_io(StepIO& io, int lane, const float* actions, float* obs, floa
 // abandons the env-step before anything is written and queues it for the wide tier (or, in the
 // reset forward, queues that forward alone).  kind DK_FORWARD (wide tier): only mj_forward + obs of
 // the stored state with ctrl 0 -- the reset forward's path through the same loop.
-template <int TASK>
+// SENS (aw_set_sensors): a separate instantiation of the step kernels that also evaluates the
+// model's sensors (stage_sensors) after the forwards whose s.touch is read; with SENS false the
+// env-step is the code it was without them.
+template <int TASK, bool SENS>
 AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lane, StepIO& io,
                      int kind = DK_STEP) {
   constexpr int NV = Tree<TASK>::NV;
@@ -602,6 +605,10 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
     if (resetting) break;
     if (!retry && check_acc<NV>(s, sl, d)) { retry = true; continue; }
     retry = false;
+    if constexpr (SENS) {
+      // sim.data.sensordata after step(): the last substep's forward (its mj_checkAcc retry included)
+      if (sub + 1 >= m.frame_skip) stage_sensors(m, s, sl, env);
+    }
     euler<TASK>(m, s, sl, Mrow, d);
     AW_PROF(s, PR_EULER);
     AW_PROF_COUNT(s, PR_SUBSTEPS);
@@ -656,6 +663,8 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
       if (rl == 0) st.status_acc[env] |= s.status & ~ST_OVF;
       defer_env(io.defer, env, DK_FORWARD, rl);
     } else {
+      // the reset / set_state forward's sensors replace the ended episode's, aligned with obs
+      if constexpr (SENS) stage_sensors(m, s, rl, env);
       if (float* ob = io.obs) write_obs(m, s, rl, ob + (size_t)env * m.obs_dim);
       if (rl == 0) {
         st.status_acc[env] |= s.status;
@@ -702,8 +711,8 @@ AW_DEV int claim_env(int* next_env, int n, int lane) {
 }
 
 // One launch = one env-step of every env (fast tier).  next_env[0..7]: the per-XCD claim
-// counters, next_env[8..]: the wide-tier queue (defer_env).
-template <int TASK>
+// counters, next_env[8..]: the wide-tier queue (defer_env).  One kernel per (task, sensors).
+template <int TASK, bool SENS>
 __global__ void __launch_bounds__(64) AW_KSTEP_ATTR k_step(DModel mval, const DModel* __restrict__ mptr, DState stval,
                                              int n, const float* __restrict__ actions,
                                              float* obs, float* reward, uint8_t* done, uint8_t* goal,
@@ -743,7 +752,7 @@ __global__ void __launch_bounds__(64) AW_KSTEP_ATTR k_step(DModel mval, const DM
   int env = xmap ? (int)((long long)n * (blockIdx.x & 7) / 8) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
   if (xmap && env >= (int)((long long)n * ((blockIdx.x & 7) + 1) / 8)) env = claim_env(next_env, n, lane);
   while (env < n) {
-    env_step<TASK>(m, s, st, env_of(env), lane, io);
+    env_step<TASK, SENS>(m, s, st, env_of(env), lane, io);
     if ((int)gridDim.x >= n) break;            // one env per workgroup: no counter
     int claim = 0;
     if (xmap) {
@@ -776,6 +785,7 @@ __global__ void __launch_bounds__(64) k_reset(DModel m, DState st, int n, const 
     defer_env(defer, env, DK_FORWARD, lane);
     return;
   }
+  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
   if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
   if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
 }
@@ -808,6 +818,7 @@ __global__ void __launch_bounds__(64) k_set_state(DModel m, DState st, int n, co
     defer_env(defer, env, DK_FORWARD, lane);
     return;
   }
+  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
   if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
   if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
 }
@@ -890,7 +901,7 @@ AW_FS_ATTR void forward_stored(const DModel& m, Env& s, const DState& st, int en
 // The claim loop is bounded by the handle's env count (the queue holds at most one entry per env and
 // launch), so every wave reaches its exit whatever the queue words hold; an entry that is not a valid
 // (env < n, kind DK_STEP / DK_FORWARD) pair is skipped -- -DAW_DEVICE_ASSERT traps instead.
-template <int TASK>
+template <int TASK, bool SENS>
 __global__ void __launch_bounds__(64) k_step_wide(const DModel* __restrict__ mptr, const float* __restrict__ actions,
                                                   float* obs, float* reward, uint8_t* done, uint8_t* goal,
                                                   float* terminal_obs, int autoreset, uint64_t seed,
@@ -930,7 +941,7 @@ __global__ void __launch_bounds__(64) k_step_wide(const DModel* __restrict__ mpt
       continue;
     }
 #endif
-    env_step<TASK>(m, s, st, env, lane, io, kind);
+    env_step<TASK, SENS>(m, s, st, env, lane, io, kind);
   }
 #ifdef AW_TRACE
   if (lane == 0) printf("wide wg %d: exit\n", (int)blockIdx.x);
@@ -1231,6 +1242,11 @@ struct aw_handle {
   std::vector<float> fault_margin0, fault_rb0;
   std::vector<double> fault_margin64_0;
   std::vector<int> fault_cls;
+  int nsensor = 0;               // the model's sensor count = its sensordata length
+  void* dsens = nullptr;         // the device SensTab (the model table's `sens`)
+  float* sensordata = nullptr;   // aw_set_sensors: [nenv][nsensor], allocated on the first enable
+  bool sensors = false;          // on: the SensTab's `out` points at sensordata and the step launches take the
+                                 // kernels that evaluate the sensors
 };
 
 #ifndef AW_TASK_TU
@@ -1245,7 +1261,7 @@ static int upload_header(aw_handle* h) {
   return AW_OK;
 }
 
-static int build_model(const Blob& B, DModel& m, MData& md) {
+static int build_model(const Blob& B, DModel& m, MData& md, SensTab& sens) {
   memset(&m, 0, sizeof(m));
   int nq = B.dim("nq"), nv = B.dim("nv"), nu = B.dim("nu"), nbody = B.dim("nbody"), njnt = B.dim("njnt");
   int ngeom_all = B.dim("ngeom"), nsite = B.dim("nsite"), ntendon = B.dim("ntendon");
@@ -1526,6 +1542,26 @@ static int build_model(const Blob& B, DModel& m, MData& md) {
   m.ntouch = (int)ts.size();
   PUT(touch_site, ts); PUT(touch_adr, ts); PUT(touch_type, ttype); PUT(touch_size, tsize);
   {
+    // every sensor in MuJoCo's order (stage_sensors): one scalar each, so nsensordata = nsensor
+    std::vector<int> stype = B.i("sensor_type"), sobj = B.i("sensor_objid"), sadr = B.i("sensor_adr");
+    nsensor = std::max(nsensor, 0);
+    if (nsensor > MAXSENS) return fail(AW_EUNSUPPORTED, "more sensors than MAXSENS");
+    if ((int)stype.size() != nsensor || (int)sobj.size() != nsensor || (int)sadr.size() != nsensor)
+      return fail(AW_EBLOB, "sensor arrays do not match nsensor");
+    for (int k = 0; k < nsensor; k++) {
+      const int lim = stype[k] == SENS_TOUCH ? nsite : stype[k] == SENS_JOINTPOS ? njnt
+                      : stype[k] == SENS_ACTUATORFRC ? nu : -1;
+      if (lim < 0) return fail(AW_EUNSUPPORTED, "sensor type (touch, jointpos and actuatorfrc are supported)");
+      if (sobj[k] < 0 || sobj[k] >= lim || sadr[k] < 0 || sadr[k] >= nsensor) return fail(AW_EBLOB, "sensor object / address out of range");
+    }
+    if (nsensor > 0 && !(B.has("site_type") && B.has("site_size"))) return fail(AW_EBLOB, "model table lacks the site shapes");
+    sens.n = nsensor;
+    sens.out = nullptr;
+    if (!put_arr(sens.type, stype) || !put_arr(sens.obj, sobj) || !put_arr(sens.adr, sadr) || !put_arr(sens.act_dof, trn) ||
+        !put_arr(sens.site_type, B.i("site_type")) || !put_arr(sens.site_size, tof(B.f("site_size"))))
+      return fail(AW_EUNSUPPORTED, "sensor tables exceed kernel capacity");
+  }
+  {
     // depth renderer: every primitive (non-mesh) geom in model order
     std::vector<int> rt, rb, rc;
     std::vector<double> rp, rq, rs, rr;
@@ -1659,15 +1695,19 @@ template <int TASK> const WideOps* wide_ops();
 template <int TASK>
 static int wide_slots(int device) {
   int per_cu = 0, cus = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_step_wide<TASK>, 64, 0);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step_wide<TASK, false>), 64, 0);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   return std::max(per_cu, 1) * std::max(cus, 1);
 }
 template <int TASK>
 static void launch_wide(aw_handle* h, const float* a, float* obs, float* rew, uint8_t* done, uint8_t* goal,
                         float* tobs, int autoreset, uint64_t seed, hipStream_t st) {
-  hipLaunchKernelGGL((k_step_wide<TASK>), dim3(h->wide_grid), dim3(64), 0, st, (const DModel*)h->dmhdr_wide, a, obs, rew,
-                     done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv);
+  if (h->sensors)
+    hipLaunchKernelGGL((k_step_wide<TASK, true>), dim3(h->wide_grid), dim3(64), 0, st, (const DModel*)h->dmhdr_wide, a, obs,
+                       rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv);
+  else
+    hipLaunchKernelGGL((k_step_wide<TASK, false>), dim3(h->wide_grid), dim3(64), 0, st, (const DModel*)h->dmhdr_wide, a, obs,
+                       rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv);
 }
 template <int TASK>
 static void launch_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, hipStream_t st) {
@@ -1686,7 +1726,7 @@ template const WideOps* wide_ops<AW_TASK_TU>();
 template <int TASK>
 static int step_slots(int device) {
   int per_cu = 0, cus = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_step<TASK>, 64, 0);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step<TASK, false>), 64, 0);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   return std::max(per_cu, 1) * std::max(cus, 1);
 }
@@ -1734,8 +1774,12 @@ static void launch_step(aw_handle* h, const float* a, float* obs, float* rew, ui
   if (grid < h->nenv && (grid & 7) == 0)   // the XCD-class claim path (k_step xmap)
     hipLaunchKernelGGL(k_order, dim3(8), dim3(1024), 0, st, reinterpret_cast<const unsigned*>(h->next_env + 10 + h->nenv),
                        h->next_env + 10 + 2 * h->nenv, h->nenv);
-  hipLaunchKernelGGL((k_step<TASK>), dim3(grid), dim3(64), 0, st, h->m, (const DModel*)h->dmhdr, h->st, h->nenv, a, obs, rew, done,
-                     goal, tobs, autoreset, seed, h->next_env);
+  if (h->sensors)   // aw_set_sensors: the instantiation that also evaluates the sensors
+    hipLaunchKernelGGL((k_step<TASK, true>), dim3(grid), dim3(64), 0, st, h->m, (const DModel*)h->dmhdr, h->st, h->nenv, a, obs,
+                       rew, done, goal, tobs, autoreset, seed, h->next_env);
+  else
+    hipLaunchKernelGGL((k_step<TASK, false>), dim3(grid), dim3(64), 0, st, h->m, (const DModel*)h->dmhdr, h->st, h->nenv, a, obs,
+                       rew, done, goal, tobs, autoreset, seed, h->next_env);
   wide_ops<TASK>()->run(h, a, obs, rew, done, goal, tobs, autoreset, seed, st);
 }
 template <int TASK>
@@ -1878,6 +1922,8 @@ static void free_handle(aw_handle* h) {
   if (h->dmhdr_wide) (void)hipFree(h->dmhdr_wide);
   if (h->jspill_wide) (void)hipFree(h->jspill_wide);
   if (h->mfac_wide) (void)hipFree(h->mfac_wide);
+  if (h->dsens) (void)hipFree(h->dsens);
+  if (h->sensordata) (void)hipFree(h->sensordata);
   delete h;
 }
 
@@ -1903,8 +1949,10 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   h->device = device;
   h->nenv = n_envs;
   std::unique_ptr<MData> md(new MData());   // value-initialised: zero
-  if (int rc = build_model(B, h->m, *md)) return rc;
+  SensTab sens = {};
+  if (int rc = build_model(B, h->m, *md, sens)) return rc;
   h->NV = h->m.nv;
+  h->nsensor = sens.n;
   if (int rc = check_tree(B, h->m.task_kind)) return rc;
   HIPCHK(hipSetDevice(device));
   HIPCHK(hipMalloc(&h->dmodel, sizeof(MData)));
@@ -1936,6 +1984,10 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
     for (int k = 0; k < h->m.nparam; k++) prm[e * np + k] = (float)def[k];
   HIPCHK(hipMemcpy(h->st.params, prm.data(), prm.size() * 4, hipMemcpyHostToDevice));
   if (int rc2 = upload_header(h.get())) return rc2;
+  // the sensor block last, so that every block above sits where it sat without it
+  HIPCHK(hipMalloc(&h->dsens, sizeof(SensTab)));
+  HIPCHK(hipMemcpy(h->dsens, &sens, sizeof(SensTab), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(((MData*)h->dmodel)->sens, &h->dsens, sizeof(void*), hipMemcpyHostToDevice));
   if (const char* e = getenv("AW_STEP_GRID")) h->grid_env = std::max(atoi(e), 0);
   if (int rc3 = update_slots(h.get())) return rc3;
   *out = h.release();
@@ -1977,6 +2029,33 @@ int aw_set_tier(aw_handle* h, int mode) {
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipDeviceSynchronize());   // queued launches read the old header
   return upload_header(h);
+}
+
+int aw_set_sensors(aw_handle* h, int enable) {
+  if (!h || enable < 0 || enable > 1) return fail(AW_EINVAL, "aw_set_sensors: enable must be 0 or 1");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // queued launches read the old table
+  const size_t bytes = (size_t)h->nenv * std::max(h->nsensor, 1) * sizeof(float);
+  if (enable && !h->sensordata) HIPCHK(hipMalloc((void**)&h->sensordata, bytes));
+  if (enable && !h->sensors) HIPCHK(hipMemset(h->sensordata, 0, bytes));   // zero until an env's next forward
+  float* out = enable ? h->sensordata : nullptr;
+  HIPCHK(hipMemcpy(&((SensTab*)h->dsens)->out, &out, sizeof(out), hipMemcpyHostToDevice));
+  h->sensors = enable != 0;
+  return AW_OK;
+}
+
+int aw_sensor_count(const aw_handle* h) {
+  if (!h) return fail(AW_EINVAL, "aw_sensor_count: null");
+  return h->nsensor;
+}
+
+int aw_sensordata(aw_handle* h, float* out, void* stream) {
+  if (!h || !out) return fail(AW_EINVAL, "aw_sensordata: null");
+  if (!h->sensors) return fail(AW_EINVAL, "aw_sensordata: sensors are disabled (aw_set_sensors)");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(out, h->sensordata, (size_t)h->nenv * h->nsensor * sizeof(float), hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+  return AW_OK;
 }
 
 int aw_set_fault(aw_handle* h, int kind, int arg) {

@@ -30,6 +30,7 @@ constexpr int MAXJB = 6;      // joints of one body (the free objects' 3 slides 
 constexpr int MAXP = 8;       // per-env model parameters
 constexpr int MAXLEV = 16;    // kinematic tree depth
 constexpr int MAXTOUCH = 4;   // task touch sensors
+constexpr int MAXSENS = 72;   // sensors of the model (Adroit: 65, hammer 66), one sensordata entry each
 constexpr int MAXPAIRCON = 8; // contacts per geom pair
 constexpr int NCLASS = 5;      // collider classes: plane-*, round-round, round-box, box-box, MPR
 
@@ -192,6 +193,7 @@ enum { GEOM_PLANE = 0, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_CYLINDER = 5, GEO
 enum { JNT_SLIDE = 2, JNT_HINGE = 3 };
 enum { C_FRIC_DOF = 0, C_FRIC_TEN = 1, C_LIM_JNT = 2, C_LIM_TEN = 3, C_CON_FRICTIONLESS = 4, C_CON_PYRAMIDAL = 5 };
 enum { S_SAT = 0, S_QUAD = 1, S_LNEG = 2, S_LPOS = 3 };
+enum { SENS_TOUCH = 0, SENS_JOINTPOS = 1, SENS_ACTUATORFRC = 2 };   // mj_envs_amd/mjcf.py SENS_TYPES
 
 // disable bits (MuJoCo 2.1 mjtDisableBit values + ours), see include/adroit_wave.h
 enum {
@@ -276,10 +278,29 @@ constexpr int COL_W = 8;      // colour record: rgb alpha specular 128*shininess
      lights; tint rows (entry, channel, param slot, scale): a colour read from the env's params */ \
   X(int, rg_site, MAXRG) X(float, rg_col, MAXRG * COL_W) X(float, light, MAXLIGHT * LIGHT_W)                  \
   X(int, tint_entry, MAXTINT) X(int, tint_chan, MAXTINT) X(int, tint_slot, MAXTINT)               \
-  X(float, tint_scale, MAXTINT)
+  X(float, tint_scale, MAXTINT)                                                                  \
+  /* the handle's sensor block (SensTab below), a device allocation of its own */                 \
+  X(const SensTab*, sens, 1)
 
 // a 16-byte record of four floats (one LDS or global access)
 typedef float MRec __attribute__((ext_vector_type(4)));
+
+// Sensors (aw_solver.h stage_sensors), read only by the kernels that evaluate them: the model's
+// sensors in MuJoCo's order -- type (SENS_*), object (touch: site, jointpos: joint, actuatorfrc:
+// actuator), sensordata address -- the sites' shapes, the dof each actuator drives, and the handle's
+// output: n = nsensor (= the sensordata length: every sensor is a scalar), out = [N][n], nullptr
+// while sensors are off (aw_set_sensors rewrites it between launches).  A device block of its own,
+// allocated after every other block of the handle and reached through MData::sens (the model
+// table's last 8 bytes), so that the model table's arrays, the header (DModel, DState) and the
+// kernels' arguments keep the sizes, offsets and places they had before there were sensors.
+struct SensTab {
+  int n;
+  float* out;
+  int type[MAXSENS], obj[MAXSENS], adr[MAXSENS];
+  int site_type[MAXS];
+  float site_size[MAXS * 3];
+  int act_dof[MAXU];
+};
 
 struct MData {
 #define AW_X(T, name, n) T name[n];
@@ -310,6 +331,9 @@ template <class T> using gp_t = __attribute__((address_space(1))) T*;
 template <class T> AW_DEV gp_t<const T> gcp(const T* p) { return (gp_t<const T>)p; }
 template <class T> AW_DEV gp_t<T> gmp(T* p) { return (gp_t<T>)p; }
 #define MDP(name, idx) ::aw::gcp(&m.d->name[idx])
+// the handle's sensor block, read like the model table (constant address space: uniform reads are
+// scalar loads); read-only for the life of a launch
+#define SENSTAB() ((const __attribute__((address_space(AW_MD_AS)))::aw::SensTab*)MD(sens, 0))
 // per-env I/O (state, actions, params, obs, episode bookkeeping): device-global like the model
 // table, so read and written through global pointers too (AW_IO_GLOBAL; 0 restores generic
 // pointers, whose flat loads also hold lgkmcnt)

@@ -516,6 +516,22 @@ AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[NV]) {
   wsync();
 }
 
+// mj_fwdActuation's scalar force of actuator u (joint transmission on dof j, gear `gear`): gain *
+// ctrl + bias after the ctrlrange and forcerange clamps, for the actuatorfrc sensors (aw_solver.h
+// stage_sensors).  The same expressions as stage_velocity below, which folds the force into
+// qfrc_smooth and drops it: that stage keeps its own text so that the step kernel without sensors
+// compiles to the instructions it had before there was a sensor stage.
+AW_DEV float actuator_force(const DModel& m, const Env& s, int u, int j, float gear) {
+  float ctrl = s.ctrl[u];
+  if (MD(act_ctrllimited, u) && !(m.disableflags & DSBL_CLAMPCTRL))
+    ctrl = clampf(ctrl, MD(act_ctrlrange, 2 * u), MD(act_ctrlrange, 2 * u + 1));
+  float len = gear * s.qpos[j], vel = gear * s.qvel[j];
+  const auto bp = MDP(act_bias, 3 * u);
+  float f = MD(act_gain, u) * ctrl + bp[0] + bp[1] * len + bp[2] * vel;
+  if (MD(act_forcelimited, u)) f = clampf(f, MD(act_forcerange, 2 * u), MD(act_forcerange, 2 * u + 1));
+  return f;
+}
+
 // mj_comVel + mj_rne(flg_acc=0) + mj_passive + mj_fwdActuation -> qfrc_smooth (lane = dof)
 AW_DEV float stage_velocity(const DModel& m, Env& s, int lane) {
   float (*cvel)[6] = s.cvel;

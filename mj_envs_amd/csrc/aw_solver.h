@@ -1462,4 +1462,74 @@ AW_DEV void stage_touch(const DModel& m, Env& s, int lane) {
   wsync();
 }
 
+// Every sensor of the model in MuJoCo's order (mj_sensorPos / mj_sensorAcc) from the forward that
+// just ran, written straight to env's row of the sensordata buffer (global, nsensor floats): nothing
+// is staged in LDS.  jointpos and actuatorfrc take one lane per sensor.  A touch pad sums like
+// stage_touch -- lane = contact, its normal force formed once for all pads, then one wave
+// reduction per pad in a fixed order (no atomics) -- with the pad's site frame built in registers
+// from xquat[body] and the constant site quaternion, exactly as stage_kinematics builds txmat, so
+// the task's own pad (hammer S_nail) gets the bits the observation clips.
+AW_DEV void stage_sensors(const DModel& m, Env& s, int lane, int env) {
+  const auto t = SENSTAB();
+  const int nsensor = t->n;
+  float* out = t->out + (size_t)env * nsensor;
+  const bool off = (m.disableflags & DSBL_SENSOR) != 0;
+  for (int k = lane; k < nsensor; k += 64) {
+    const int ty = t->type[k], obj = t->obj[k];
+    if (ty == SENS_TOUCH) continue;
+    float v = 0.f;
+    if (ty == SENS_JOINTPOS) v = s.qpos[obj];
+    else if (!(m.disableflags & DSBL_ACTUATION)) v = actuator_force(m, s, obj, t->act_dof[obj], MD(act_gear, obj));
+    GOUT(out)[t->adr[k]] = off ? 0.f : v;
+  }
+  float fn[NCH];
+  int cb1[NCH], cb2[NCH];
+#pragma unroll
+  for (int h = 0; h < NCH; h++) {
+    const int c = lane + 64 * h;
+    fn[h] = 0.f;
+    cb1[h] = cb2[h] = -1;
+    if (c < s.ncon && s.con_efc[c] >= 0 && !off) {
+      const int pr = s.con_pair[c];
+      cb1[h] = MD(geom_bodyid, MD(cp_g1, pr));
+      cb2[h] = MD(geom_bodyid, MD(cp_g2, pr));
+      const int adr = s.con_efc[c], dim = MD(cp_condim, pr);
+      float f = 0.f;
+      if (dim == 1) f = s.efc_force[adr];
+      else for (int j = 0; j < 2 * (dim - 1); j++) f += s.efc_force[adr + j];
+      fn[h] = f;
+    }
+  }
+  for (int k = 0; k < nsensor; k++) {
+    if (t->type[k] != SENS_TOUCH) continue;
+    const int site = t->obj[k], bid = MD(site_bodyid, site);
+    float val = 0.f;
+    bool mine = false;   // a pressing contact of this lane on the pad's body
+#pragma unroll
+    for (int h = 0; h < NCH; h++) mine = mine || (fn[h] > 0.f && (bid == cb1[h] || bid == cb2[h]));
+    if (__ballot(mine)) {   // most pads carry no contact: their sum is an exact 0
+      float q[4], sq[4], mat[9];
+      for (int c = 0; c < 4; c++) sq[c] = MD(site_quat, 4 * site + c);
+      mulq(q, s.xquat[bid], sq);
+      q2m(mat, q);
+      const float tsz[3] = {t->site_size[3 * site], t->site_size[3 * site + 1], t->site_size[3 * site + 2]};
+      const int stype = t->site_type[site];
+#pragma unroll
+      for (int h = 0; h < NCH; h++) {
+        const int c = lane + 64 * h;
+        if (fn[h] > 0.f && (bid == cb1[h] || bid == cb2[h])) {
+          float ray[3];
+          copy3(ray, s.con_nrm[c]);
+          normalize3(ray);
+          if (bid == cb2[h]) scl3(ray, ray, -1.f);
+          if (ray_geom(s.sxpos[site], mat, tsz, s.con_pos[c], ray, stype) >= 0.f) val += fn[h];
+        }
+      }
+    }
+    const float tot = wave_sum(val);
+    if (lane == 0) GOUT(out)[t->adr[k]] = tot;
+  }
+  wsync();
+}
+
 }  // namespace aw

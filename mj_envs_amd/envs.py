@@ -56,7 +56,7 @@ class AdroitVecEnv:
     """``num_envs`` envs of ``env_id`` on GPU ``device``; every buffer stays in HBM."""
 
     def __init__(self, env_id: str, num_envs: int, device: int = 0, variation_type: Optional[str] = None,
-                 seed: int = 1, autoreset: bool = True):
+                 seed: int = 1, autoreset: bool = True, sensors: bool = False):
         import torch
         self.env_id = env_id
         self.spec = TASKS[env_id]
@@ -80,6 +80,35 @@ class AdroitVecEnv:
         self.terminal_obs = s.empty(num_envs, self.obs_dim)
         self._status = s.empty(num_envs, dtype=torch.int32)
         self._resets = 0
+        # MuJoCo's sensordata (the reference's env.sim.data.sensordata), opt-in: the model's sensors
+        # in declared order, refreshed by step / reset / set_state into one device tensor
+        self.sensors = bool(sensors)
+        if self.sensors:
+            from .mjcf import SENS_TOUCH
+            s.set_sensors(True)
+            self._sensordata = torch.zeros(num_envs, s.nsensordata, device=s.torch_device)
+            order = np.argsort(self.model.arrays["sensor_adr"])
+            self.sensor_names = [self.model.names["sensor"][i] for i in order]
+            self.sensor_types = self.model.arrays["sensor_type"][order].astype(np.int32)   # mjcf.SENS_*
+            self._touch_cols = torch.as_tensor(np.flatnonzero(self.sensor_types == SENS_TOUCH), device=s.torch_device)
+
+    def _no_sensors(self, what):
+        raise AttributeError(f"{what}: this env was created with sensors=False")
+
+    @property
+    def sensordata(self):
+        """[N, nsensordata] device tensor (fp32) of the last step / reset / set_state: actuator forces,
+        touch pads and joint positions as ``sim.data.sensordata`` orders them (``sensor_names``)"""
+        return self._sensordata if self.sensors else self._no_sensors("sensordata")
+
+    @property
+    def touch(self):
+        """the touch-type columns of ``sensordata`` in sensor order: a new [N, ntouch] tensor"""
+        return self._sensordata[:, self._touch_cols] if self.sensors else self._no_sensors("touch")
+
+    def _read_sensors(self):
+        if self.sensors:
+            self.sim.sensordata(self._sensordata)
 
     # --- episode control -------------------------------------------------------------------
     def reset(self, mask=None, params=None, seed: Optional[int] = None):
@@ -88,6 +117,7 @@ class AdroitVecEnv:
             seed = self.seed + 7919 * self._resets
         self._resets += 1
         self.sim.reset(self.obs, params=params, mask=mask, seed=seed)
+        self._read_sensors()
         return self.obs
 
     def step(self, actions):
@@ -100,6 +130,9 @@ class AdroitVecEnv:
         self.sim.status(last=self._status)
         info = {"goal_achieved": self.goal.bool(), "terminal_obs": self.terminal_obs,
                 "status": self._status}    # AW_ST_* flags of this step (NaN reset, overflow)
+        if self.sensors:
+            self._read_sensors()
+            info["sensordata"] = self._sensordata
         return self.obs, self.reward, terminated, truncated, info
 
     def random_actions(self, out, step: int, seed: int = 0):
@@ -158,6 +191,7 @@ class AdroitVecEnv:
 
     def set_state(self, qpos=None, qvel=None, qacc_warmstart=None, params=None):
         self.sim.set_state(qpos, qvel, qacc_warmstart, params, obs=self.obs)
+        self._read_sensors()
         return self.obs
 
     def episode_stats(self):
@@ -211,14 +245,15 @@ class _AdroitEnv(_reference_base()):
     env_id: str = ""
 
     def __init__(self, render_mode=None, width: int = 64, height: int = 64, is_headless: bool = True,
-                 variation_type: Optional[str] = None, device: int = 0, seed: Optional[int] = None):
+                 variation_type: Optional[str] = None, device: int = 0, seed: Optional[int] = None,
+                 sensors: bool = False):
         import torch
         self.render_mode, self.width, self.height = render_mode, width, height
         self.is_headless = is_headless
         self.variation_type = variation_type
         self.observer = None            # the camera record once mj_viewer_headless_setup() ran
         self.vec = AdroitVecEnv(self.env_id, 1, device=device, variation_type=variation_type,
-                                seed=1, autoreset=False)
+                                seed=1, autoreset=False, sensors=sensors)
         self.vec._facade = self         # camera flags (pen's use_aerial_view) of this facade
         self.model = self.vec.model
         self.frame_skip = self.vec.frame_skip
@@ -263,6 +298,12 @@ class _AdroitEnv(_reference_base()):
 
     def get_obs(self):
         return self._obs.copy()
+
+    @property
+    def sensordata(self):
+        """``self.data.sensordata`` of the reference: float64 [nsensordata] of the last step / reset /
+        set_env_state (needs ``sensors=True``)"""
+        return self.vec.sensordata[0].cpu().numpy().astype(np.float64)
 
     def _params(self) -> np.ndarray:
         return self.vec.get_state()["params"][0].cpu().numpy().astype(np.float64)

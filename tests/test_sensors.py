@@ -1,0 +1,88 @@
+"""MuJoCo sensordata on device: the C-ABI surface and the calibration of the test inputs (CPU).
+
+The GPU tests (tests/test_gpu_sensors.py) compare touch pads against the fp64 oracle on DAPG-driven
+states.  A pad is a sum of a few contact forces, and near an impact the reference itself moves by
+tens of per cent when its input is rounded to fp32; test_inputs_are_well_conditioned asserts that
+the chosen env-steps are not such states, so a GPU miss there is the GPU's.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ENVS, REPO, load_task_model
+import sensor_states as ss
+
+NEW = ("aw_set_sensors", "aw_sensor_count", "aw_sensordata")
+
+
+def test_header_and_exports_list_the_sensor_calls():
+    from mj_envs_amd import _native
+    src = open(os.path.join(REPO, "include", "adroit_wave.h")).read()
+    declared = set(re.findall(r"^\s*(?:int|const char\*)\s+(aw_\w+)\s*\(", src, re.M))
+    for name in NEW:
+        assert name in declared, name
+        assert name in _native.EXPORTS, name
+        assert hasattr(_native.load(), name), name
+    # existing signatures and the dims enum are as they were
+    assert _native.AW_NDIMS == 21 and "AW_DIM_WIDE_GRID, AW_NDIMS" in src
+
+
+@pytest.mark.parametrize("env_id", ENVS)
+def test_sensor_count_is_the_models(env_id):
+    """aw_sensor_count's expected value: nsensor of the model (65, hammer 66), one scalar per sensor,
+    within the kernel's table (MAXSENS 72), of the three types the stage evaluates"""
+    m = load_task_model(env_id)
+    assert m.nsensor == (66 if env_id == "hammer-v0" else 65)
+    assert m.nsensor == m.nsensordata == len(m.arrays["sensor_adr"]) <= 72
+    assert sorted(m.arrays["sensor_adr"]) == list(range(m.nsensor))
+    types = m.arrays["sensor_type"]
+    assert set(types) == {ss.SENS_TOUCH, ss.SENS_JOINTPOS, ss.SENS_ACTUATORFRC}
+    assert (types == ss.SENS_ACTUATORFRC).sum() == 20 and (types == ss.SENS_JOINTPOS).sum() == 24
+    assert (types == ss.SENS_TOUCH).sum() == m.nsensor - 44
+    src = open(os.path.join(REPO, "mj_envs_amd", "csrc", "aw_common.h")).read()
+    assert int(re.search(r"MAXSENS = (\d+)", src).group(1)) >= m.nsensor
+
+
+def test_unknown_sensor_type_fails_create():
+    """a sensor the stage cannot evaluate is an error of aw_create (the model table is checked
+    before any device call), not a silently missing entry"""
+    import ctypes
+    from mj_envs_amd import _native
+    L = _native.load()
+    m = load_task_model("door-v0")
+    m.arrays["sensor_type"] = m.arrays["sensor_type"].copy()
+    m.arrays["sensor_type"][3] = 9
+    blob = m.to_blob()
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    h = ctypes.c_void_p()
+    assert L.aw_create(buf, len(blob), 1, 0, ctypes.byref(h)) == -5      # AW_EUNSUPPORTED
+    assert b"sensor type" in L.aw_last_error()
+
+
+@pytest.mark.parametrize("env_id", ENVS)
+def test_inputs_are_well_conditioned(env_id):
+    """On the oracle alone: the DAPG states fire enough pads, and no firing pad moves by more than
+    5e-4 |v| + 5e-4 or flips on / off when state, params and ctrl are rounded to fp32"""
+    d = ss.dapg_states(env_id)
+    types, _ = ss.sensor_layout(d["m"])
+    tcols = np.flatnonzero(types == ss.SENS_TOUCH)
+    ex = np.stack(d["sens_exact"])[:, :, tcols]     # [step, env, pad]
+    rd = np.stack(d["sens_f32"])[:, :, tcols]
+    firing = ex > 0
+    moved = np.abs(rd - ex) > 5e-4 * np.abs(ex) + 5e-4
+    flipped = (rd > 0) != firing
+    relmax = (np.abs(rd - ex)[firing] / ex[firing]).max() if firing.any() else 0.0
+    print(f"{env_id}: {int(firing.sum())} firing (env, step, pad) cases, {int(firing.any(axis=(0, 1)).sum())} distinct "
+          f"pads, max relative move under fp32 rounding {relmax:.2e}, moved {int(moved.sum())}, flipped {int(flipped.sum())}")
+    assert firing.sum() >= 20
+    assert firing.any(axis=(0, 1)).sum() >= 5
+    assert not moved.any() and not flipped.any()
+
+
+def test_hammer_nail_fires_under_dapg():
+    """the state of the GPU consistency test exists: some env-step leaves S_nail > 0 on the oracle"""
+    found = ss.first_nail_state()
+    assert found is not None
+    print(f"S_nail first fires after env-step {found[6]} in env {found[7]}")
