@@ -117,6 +117,42 @@ int aw_set_sensors(aw_handle* h, int enable);
 int aw_sensor_count(const aw_handle* h);
 int aw_sensordata(aw_handle* h, float* out, void* stream);
 
+/* Batched mjData views (sim.data of the reference after step() / reset() / set_env_state()): body
+ * and site frames, qacc, the constraint force, the solver's counts, and the contact list with
+ * mj_contactForce's forces, for every env, written by the step / reset / set_state kernels straight
+ * into the CALLER's device buffers -- there is no copy call.  Off by default.  aw_set_data(h, groups,
+ * max_contacts, bufs) selects the groups (an OR of AW_DATA_*; 0 disables and ignores the rest) and
+ * the instantiation of the step kernels that also writes them; with data off the step is the kernel
+ * it was.  Every buffer of a requested group must be device memory that stays valid until data is
+ * disabled or the handle destroyed; buffers of groups not requested are ignored (may be NULL) and
+ * never written.  Values are those of the last mj_forward before the last integration of the
+ * env-step (the lag obs has); an env that auto-reset in a step holds its reset forward's values,
+ * aligned with obs.  A buffer row keeps its content until the env's next step, reset or set_state.
+ *   AW_DATA_KIN      xpos [N][nbody][3], xquat [N][nbody][4], site_xpos [N][nsite][3]   (fp32)
+ *   AW_DATA_DYN      qacc [N][nv], qfrc_constraint [N][nv] (fp32), counts int32 [N][4] = ncon, nefc,
+ *                    Newton iterations, noslip iterations; ncon is the forward's count even when it
+ *                    exceeds max_contacts
+ *   AW_DATA_CONTACT  contact [N][max_contacts] records of AW_CONTACT_DWORDS 32-bit words (64 bytes:
+ *                    64 max_contacts bytes per env, 134 MB at 65 536 envs with max_contacts 32; DAPG
+ *                    grasps reach 12 contacts).  Only records < min(ncon, max_contacts) of an env
+ *                    are written, in mj_collision's order; memory past them is left as it was.
+ * Contact record: float dist, pos[3], normal[3] (unit, geom1 -> geom2), force[3] (contact frame:
+ * normal, then the two tangents of mju_makeFrame(normal); mj_contactForce from efc_force after
+ * noslip), torsion (condim 4's third component), mu (sliding friction); int32 geom1, geom2 (model
+ * geom ids), dim, efc_address (-1 and zero force: a contact without constraint rows).
+ * AW_EINVAL: unknown group bits, a NULL buffer of a requested group, max_contacts < 1 or above the
+ * wide tier's contact storage (AW_DATA_MAX_CONTACTS).  Waits for the device.  Sensors and data may be
+ * on together. */
+enum { AW_DATA_KIN = 1, AW_DATA_DYN = 2, AW_DATA_CONTACT = 4 };
+#define AW_CONTACT_DWORDS 16
+#define AW_DATA_MAX_CONTACTS 128
+typedef struct {
+  float *xpos, *xquat, *site_xpos, *qacc, *qfrc_constraint;
+  int32_t* counts;
+  void* contact;
+} aw_data_bufs;
+int aw_set_data(aw_handle* h, int groups, int max_contacts, const aw_data_bufs* bufs);
+
 /* Reset envs (mask[e] != 0, or all if mask == NULL): qpos = qpos0, qvel = 0, warmstart = 0,
  * per-env model params from `params` [N][nparam] or, if NULL, sampled on device (Philox,
  * keyed by seed, global env id and episode count) from the reference reset distribution;

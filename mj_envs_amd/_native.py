@@ -45,8 +45,47 @@ AW_DUMP_SIZE_WIDE = 1768 + 14 * WIDE_MAXCON_STORE + 5 * WIDE_MAXEFC
 NT_EXIT = ("max_iterations", "no_descent", "fp32_noise_floor", "improvement", "gradient", "no_constraints")
 AW_DUMP_SIZE = 1768 + 14 * MAXCON + 5 * MAXEFC
 
+# batched mjData views (include/adroit_wave.h aw_set_data): group bits, the contact record's size in
+# 32-bit words and its fields as (first word, words, is_int), the largest max_contacts
+AW_DATA_KIN, AW_DATA_DYN, AW_DATA_CONTACT = 1, 2, 4
+AW_DATA_ALL = AW_DATA_KIN | AW_DATA_DYN | AW_DATA_CONTACT
+DATA_GROUPS = {"kin": AW_DATA_KIN, "dyn": AW_DATA_DYN, "contact": AW_DATA_CONTACT}
+AW_CONTACT_DWORDS = 16
+AW_DATA_MAX_CONTACTS = 128
+CONTACT_FIELDS = dict(dist=(0, 1, False), pos=(1, 3, False), normal=(4, 3, False), force=(7, 3, False),
+                      torsion=(10, 1, False), mu=(11, 1, False), geom1=(12, 1, True), geom2=(13, 1, True),
+                      dim=(14, 1, True), efc_address=(15, 1, True))
+# the buffers of each group, in aw_data_bufs' order
+DATA_BUFFERS = {AW_DATA_KIN: ("xpos", "xquat", "site_xpos"), AW_DATA_DYN: ("qacc", "qfrc_constraint", "counts"),
+                AW_DATA_CONTACT: ("contact",)}
+
 _lib = None
 _vp = ctypes.c_void_p
+
+
+class DataBufs(ctypes.Structure):
+    """aw_data_bufs: the caller's device buffers of aw_set_data"""
+    _fields_ = [(k, _vp) for k in ("xpos", "xquat", "site_xpos", "qacc", "qfrc_constraint", "counts", "contact")]
+
+
+def data_groups(data) -> int:
+    """AW_DATA_* mask of ``data``: False / None -> 0, True -> every group, a group name or an
+    iterable of them ("kin", "dyn", "contact"), or the mask itself"""
+    if data is None or data is False:
+        return 0
+    if data is True:
+        return AW_DATA_ALL
+    if isinstance(data, int):
+        if data & ~AW_DATA_ALL or data < 0:
+            raise ValueError(f"data: unknown group bits in {data}")
+        return data
+    names = (data,) if isinstance(data, str) else tuple(data)
+    g = 0
+    for k in names:
+        if k not in DATA_GROUPS:
+            raise ValueError(f"data: unknown group {k!r} (one of {sorted(DATA_GROUPS)})")
+        g |= DATA_GROUPS[k]
+    return g
 
 
 class NativeError(RuntimeError):
@@ -77,6 +116,9 @@ def load():
         L.aw_sensordata.argtypes = [_vp, _vp, _vp]
         for f in ("aw_set_sensors", "aw_sensor_count", "aw_sensordata"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "aw_set_data"):
+        L.aw_set_data.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DataBufs)]
+        L.aw_set_data.restype = ctypes.c_int
     if hasattr(L, "aw_forward_dump_wide"):
         L.aw_forward_dump_wide.argtypes = [_vp, ctypes.c_int, _vp, _vp, _vp]
         L.aw_forward_dump_wide.restype = ctypes.c_int
@@ -121,7 +163,7 @@ def load():
 
 
 EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier", "aw_set_fault", "aw_reset", "aw_step",
-           "aw_set_sensors", "aw_sensor_count", "aw_sensordata",
+           "aw_set_sensors", "aw_sensor_count", "aw_sensordata", "aw_set_data",
            "aw_random_actions", "aw_set_env_offset", "aw_get_state", "aw_set_state", "aw_status",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
@@ -257,6 +299,40 @@ class Sim:
         assert tuple(out.shape) == (self.n_envs, self.nsensordata) and out.dtype == torch.float32 and \
             out.is_contiguous(), "sensordata: out must be fp32 [n_envs, nsensordata]"
         _check(load().aw_sensordata(self.h, _ptr(out), _stream()))
+        return out
+
+    def set_data(self, groups, max_contacts: int = 32, bufs: Optional[dict] = None):
+        """Batched mjData views on or off (include/adroit_wave.h aw_set_data).  ``groups``: an
+        AW_DATA_* mask, True, or group names ("kin", "dyn", "contact"); 0 / False disables.  Allocates
+        the requested groups' device tensors (zero until an env's next step, reset or set_state),
+        keeps them alive for as long as the kernels write them, and returns them by name: xpos
+        [N, nbody, 3], xquat [N, nbody, 4], site_xpos [N, nsite, 3], qacc / qfrc_constraint [N, nv]
+        (fp32), counts [N, 4] (int32: ncon, nefc, Newton iterations, noslip iterations), contact
+        [N, max_contacts, AW_CONTACT_DWORDS] (fp32 words; CONTACT_FIELDS; the integer fields are
+        read with ``.view(torch.int32)``).  ``bufs`` supplies tensors of the caller's instead
+        (contiguous, at least those sizes): the kernels write them in place."""
+        import torch
+        g = data_groups(groups)
+        n, K = self.n_envs, int(max_contacts)
+        shapes = dict(xpos=(n, self.nbody, 3), xquat=(n, self.nbody, 4), site_xpos=(n, self.nsite, 3),
+                      qacc=(n, self.nv), qfrc_constraint=(n, self.nv), counts=(n, 4),
+                      contact=(n, max(K, 0), AW_CONTACT_DWORDS))
+        out, c = {}, DataBufs()
+        if g and 1 <= K <= AW_DATA_MAX_CONTACTS:      # (the library reports a bad max_contacts)
+            for bit, names in DATA_BUFFERS.items():
+                if not g & bit:
+                    continue
+                for k in names:
+                    dt = torch.int32 if k == "counts" else torch.float32
+                    t = bufs[k] if bufs and k in bufs else torch.zeros(shapes[k], dtype=dt, device=self.torch_device)
+                    need = int(np.prod(shapes[k]))
+                    assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() >= need, \
+                        f"set_data: {k} must be a contiguous {dt} device tensor of >= {need} elements"
+                    out[k] = t
+                    setattr(c, k, t.data_ptr())
+        _check(load().aw_set_data(self.h, g, K, ctypes.byref(c)))
+        self._data_bufs = out                         # the kernels write these until the next set_data
+        self.data_groups, self.max_contacts = g, K
         return out
 
     def set_fault(self, kind: int, arg: int = 0):

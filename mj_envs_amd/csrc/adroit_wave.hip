@@ -555,8 +555,9 @@ AW_DEV void park_io(StepIO& io, int lane, const float* actions, float* obs, floa
 // the stored state with ctrl 0 -- the reset forward's path through the same loop.
 // SENS (aw_set_sensors): a separate instantiation of the step kernels that also evaluates the
 // model's sensors (stage_sensors) after the forwards whose s.touch is read; with SENS false the
-// env-step is the code it was without them.
-template <int TASK, bool SENS>
+// env-step is the code it was without them.  DATA (aw_set_data): likewise for the batched mjData
+// views (stage_data), at the same places.
+template <int TASK, bool SENS, bool DATA>
 AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lane, StepIO& io,
                      int kind = DK_STEP) {
   constexpr int NV = Tree<TASK>::NV;
@@ -608,6 +609,9 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
     if constexpr (SENS) {
       // sim.data.sensordata after step(): the last substep's forward (its mj_checkAcc retry included)
       if (sub + 1 >= m.frame_skip) stage_sensors(m, s, sl, env);
+    }
+    if constexpr (DATA) {
+      if (sub + 1 >= m.frame_skip) stage_data(m, s, sl, env, d.qacc, d.qfrc_con);
     }
     euler<TASK>(m, s, sl, Mrow, d);
     AW_PROF(s, PR_EULER);
@@ -665,6 +669,7 @@ AW_DEV void env_step(const DModel& m, Env& s, const DState& st, int env, int lan
     } else {
       // the reset / set_state forward's sensors replace the ended episode's, aligned with obs
       if constexpr (SENS) stage_sensors(m, s, rl, env);
+      if constexpr (DATA) stage_data(m, s, rl, env, d.qacc, d.qfrc_con);
       if (float* ob = io.obs) write_obs(m, s, rl, ob + (size_t)env * m.obs_dim);
       if (rl == 0) {
         st.status_acc[env] |= s.status;
@@ -711,8 +716,8 @@ AW_DEV int claim_env(int* next_env, int n, int lane) {
 }
 
 // One launch = one env-step of every env (fast tier).  next_env[0..7]: the per-XCD claim
-// counters, next_env[8..]: the wide-tier queue (defer_env).  One kernel per (task, sensors).
-template <int TASK, bool SENS>
+// counters, next_env[8..]: the wide-tier queue (defer_env).  One kernel per (task, sensors, data).
+template <int TASK, bool SENS, bool DATA>
 __global__ void __launch_bounds__(64) AW_KSTEP_ATTR k_step(DModel mval, const DModel* __restrict__ mptr, DState stval,
                                              int n, const float* __restrict__ actions,
                                              float* obs, float* reward, uint8_t* done, uint8_t* goal,
@@ -752,7 +757,7 @@ __global__ void __launch_bounds__(64) AW_KSTEP_ATTR k_step(DModel mval, const DM
   int env = xmap ? (int)((long long)n * (blockIdx.x & 7) / 8) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
   if (xmap && env >= (int)((long long)n * ((blockIdx.x & 7) + 1) / 8)) env = claim_env(next_env, n, lane);
   while (env < n) {
-    env_step<TASK, SENS>(m, s, st, env_of(env), lane, io);
+    env_step<TASK, SENS, DATA>(m, s, st, env_of(env), lane, io);
     if ((int)gridDim.x >= n) break;            // one env per workgroup: no counter
     int claim = 0;
     if (xmap) {
@@ -786,6 +791,7 @@ __global__ void __launch_bounds__(64) k_reset(DModel m, DState st, int n, const 
     return;
   }
   if (SENSTAB()->out) stage_sensors(m, s, lane, env);
+  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
   if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
   if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
 }
@@ -819,6 +825,7 @@ __global__ void __launch_bounds__(64) k_set_state(DModel m, DState st, int n, co
     return;
   }
   if (SENSTAB()->out) stage_sensors(m, s, lane, env);
+  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
   if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
   if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
 }
@@ -901,7 +908,7 @@ AW_FS_ATTR void forward_stored(const DModel& m, Env& s, const DState& st, int en
 // The claim loop is bounded by the handle's env count (the queue holds at most one entry per env and
 // launch), so every wave reaches its exit whatever the queue words hold; an entry that is not a valid
 // (env < n, kind DK_STEP / DK_FORWARD) pair is skipped -- -DAW_DEVICE_ASSERT traps instead.
-template <int TASK, bool SENS>
+template <int TASK, bool SENS, bool DATA>
 __global__ void __launch_bounds__(64) k_step_wide(const DModel* __restrict__ mptr, const float* __restrict__ actions,
                                                   float* obs, float* reward, uint8_t* done, uint8_t* goal,
                                                   float* terminal_obs, int autoreset, uint64_t seed,
@@ -941,7 +948,7 @@ __global__ void __launch_bounds__(64) k_step_wide(const DModel* __restrict__ mpt
       continue;
     }
 #endif
-    env_step<TASK, SENS>(m, s, st, env, lane, io, kind);
+    env_step<TASK, SENS, DATA>(m, s, st, env, lane, io, kind);
   }
 #ifdef AW_TRACE
   if (lane == 0) printf("wide wg %d: exit\n", (int)blockIdx.x);
@@ -1247,6 +1254,9 @@ struct aw_handle {
   float* sensordata = nullptr;   // aw_set_sensors: [nenv][nsensor], allocated on the first enable
   bool sensors = false;          // on: the SensTab's `out` points at sensordata and the step launches take the
                                  // kernels that evaluate the sensors
+  void* ddata = nullptr;         // the device DataTab (the model table's `data`)
+  int data_groups = 0;           // aw_set_data: the AW_DATA_* groups the kernels write (0: off) into the caller's
+                                 // buffers; nonzero selects the step kernels with stage_data
 };
 
 #ifndef AW_TASK_TU
@@ -1261,7 +1271,7 @@ static int upload_header(aw_handle* h) {
   return AW_OK;
 }
 
-static int build_model(const Blob& B, DModel& m, MData& md, SensTab& sens) {
+static int build_model(const Blob& B, DModel& m, MData& md, SensTab& sens, DataTab& data) {
   memset(&m, 0, sizeof(m));
   int nq = B.dim("nq"), nv = B.dim("nv"), nu = B.dim("nu"), nbody = B.dim("nbody"), njnt = B.dim("njnt");
   int ngeom_all = B.dim("ngeom"), nsite = B.dim("nsite"), ntendon = B.dim("ntendon");
@@ -1389,6 +1399,9 @@ static int build_model(const Blob& B, DModel& m, MData& md, SensTab& sens) {
   PUT(geom_pos64, cpos64); PUT(geom_quat64, cquat64); PUT(geom_size64, csize64);
   m.ngeom = (int)ctype.size();
   if (m.ngeom > MAXG) return fail(AW_EUNSUPPORTED, "too many collidable geoms");
+  memset(&data, 0, sizeof(data));   // stage_data's table: off, and the model geom id of each collidable geom
+  for (int g = 0; g < ngeom_all; g++)
+    if (gmap[g] >= 0) data.geom_id[gmap[g]] = g;
   PUT(geom_type, ctype); PUT(geom_bodyid, cbody); PUT(geom_pos, cpos);
   PUT(geom_quat, cquat); PUT(geom_size, csize); PUT(geom_rbound, crb);
 
@@ -1695,19 +1708,22 @@ template <int TASK> const WideOps* wide_ops();
 template <int TASK>
 static int wide_slots(int device) {
   int per_cu = 0, cus = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step_wide<TASK, false>), 64, 0);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step_wide<TASK, false, false>), 64, 0);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   return std::max(per_cu, 1) * std::max(cus, 1);
 }
 template <int TASK>
 static void launch_wide(aw_handle* h, const float* a, float* obs, float* rew, uint8_t* done, uint8_t* goal,
                         float* tobs, int autoreset, uint64_t seed, hipStream_t st) {
-  if (h->sensors)
-    hipLaunchKernelGGL((k_step_wide<TASK, true>), dim3(h->wide_grid), dim3(64), 0, st, (const DModel*)h->dmhdr_wide, a, obs,
-                       rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv);
-  else
-    hipLaunchKernelGGL((k_step_wide<TASK, false>), dim3(h->wide_grid), dim3(64), 0, st, (const DModel*)h->dmhdr_wide, a, obs,
-                       rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv);
+#define AW_LAUNCH_WIDE(S, D)                                                                                          \
+  hipLaunchKernelGGL((k_step_wide<TASK, S, D>), dim3(h->wide_grid), dim3(64), 0, st, (const DModel*)h->dmhdr_wide, a, \
+                     obs, rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv)
+  if (h->data_groups) {   // aw_set_data: the instantiations that also write the mjData views
+    if (h->sensors) AW_LAUNCH_WIDE(true, true); else AW_LAUNCH_WIDE(false, true);
+  } else {
+    if (h->sensors) AW_LAUNCH_WIDE(true, false); else AW_LAUNCH_WIDE(false, false);
+  }
+#undef AW_LAUNCH_WIDE
 }
 template <int TASK>
 static void launch_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, hipStream_t st) {
@@ -1726,7 +1742,7 @@ template const WideOps* wide_ops<AW_TASK_TU>();
 template <int TASK>
 static int step_slots(int device) {
   int per_cu = 0, cus = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step<TASK, false>), 64, 0);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step<TASK, false, false>), 64, 0);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   return std::max(per_cu, 1) * std::max(cus, 1);
 }
@@ -1774,12 +1790,16 @@ static void launch_step(aw_handle* h, const float* a, float* obs, float* rew, ui
   if (grid < h->nenv && (grid & 7) == 0)   // the XCD-class claim path (k_step xmap)
     hipLaunchKernelGGL(k_order, dim3(8), dim3(1024), 0, st, reinterpret_cast<const unsigned*>(h->next_env + 10 + h->nenv),
                        h->next_env + 10 + 2 * h->nenv, h->nenv);
-  if (h->sensors)   // aw_set_sensors: the instantiation that also evaluates the sensors
-    hipLaunchKernelGGL((k_step<TASK, true>), dim3(grid), dim3(64), 0, st, h->m, (const DModel*)h->dmhdr, h->st, h->nenv, a, obs,
-                       rew, done, goal, tobs, autoreset, seed, h->next_env);
-  else
-    hipLaunchKernelGGL((k_step<TASK, false>), dim3(grid), dim3(64), 0, st, h->m, (const DModel*)h->dmhdr, h->st, h->nenv, a, obs,
-                       rew, done, goal, tobs, autoreset, seed, h->next_env);
+  // aw_set_sensors / aw_set_data: the instantiation that also evaluates the sensors / writes the mjData views
+#define AW_LAUNCH_STEP(S, D)                                                                                          \
+  hipLaunchKernelGGL((k_step<TASK, S, D>), dim3(grid), dim3(64), 0, st, h->m, (const DModel*)h->dmhdr, h->st, h->nenv, a, \
+                     obs, rew, done, goal, tobs, autoreset, seed, h->next_env)
+  if (h->data_groups) {
+    if (h->sensors) AW_LAUNCH_STEP(true, true); else AW_LAUNCH_STEP(false, true);
+  } else {
+    if (h->sensors) AW_LAUNCH_STEP(true, false); else AW_LAUNCH_STEP(false, false);
+  }
+#undef AW_LAUNCH_STEP
   wide_ops<TASK>()->run(h, a, obs, rew, done, goal, tobs, autoreset, seed, st);
 }
 template <int TASK>
@@ -1923,6 +1943,7 @@ static void free_handle(aw_handle* h) {
   if (h->jspill_wide) (void)hipFree(h->jspill_wide);
   if (h->mfac_wide) (void)hipFree(h->mfac_wide);
   if (h->dsens) (void)hipFree(h->dsens);
+  if (h->ddata) (void)hipFree(h->ddata);
   if (h->sensordata) (void)hipFree(h->sensordata);
   delete h;
 }
@@ -1950,7 +1971,8 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   h->nenv = n_envs;
   std::unique_ptr<MData> md(new MData());   // value-initialised: zero
   SensTab sens = {};
-  if (int rc = build_model(B, h->m, *md, sens)) return rc;
+  DataTab data = {};
+  if (int rc = build_model(B, h->m, *md, sens, data)) return rc;
   h->NV = h->m.nv;
   h->nsensor = sens.n;
   if (int rc = check_tree(B, h->m.task_kind)) return rc;
@@ -1988,6 +2010,9 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   HIPCHK(hipMalloc(&h->dsens, sizeof(SensTab)));
   HIPCHK(hipMemcpy(h->dsens, &sens, sizeof(SensTab), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(((MData*)h->dmodel)->sens, &h->dsens, sizeof(void*), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&h->ddata, sizeof(DataTab)));   // and the mjData output block after it (aw_set_data)
+  HIPCHK(hipMemcpy(h->ddata, &data, sizeof(DataTab), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(((MData*)h->dmodel)->data, &h->ddata, sizeof(void*), hipMemcpyHostToDevice));
   if (const char* e = getenv("AW_STEP_GRID")) h->grid_env = std::max(atoi(e), 0);
   if (int rc3 = update_slots(h.get())) return rc3;
   *out = h.release();
@@ -2041,6 +2066,39 @@ int aw_set_sensors(aw_handle* h, int enable) {
   float* out = enable ? h->sensordata : nullptr;
   HIPCHK(hipMemcpy(&((SensTab*)h->dsens)->out, &out, sizeof(out), hipMemcpyHostToDevice));
   h->sensors = enable != 0;
+  return AW_OK;
+}
+
+static_assert(AW_DATA_MAX_CONTACTS == WIDE_MAXCON, "aw_set_data's contact cap is the wide tier's contact storage");
+static_assert(AW_CONTACT_DWORDS * 4 == 4 * sizeof(MRec), "a contact record is four 16-byte stores");
+int aw_set_data(aw_handle* h, int groups, int max_contacts, const aw_data_bufs* bufs) {
+  if (!h) return fail(AW_EINVAL, "aw_set_data: null");
+  if (groups & ~(AW_DATA_KIN | AW_DATA_DYN | AW_DATA_CONTACT)) return fail(AW_EINVAL, "aw_set_data: unknown group bits");
+  // the table's head (groups, capacity, buffers); geom_id behind it stays as aw_create wrote it
+  DataTab t;
+  memset(&t, 0, sizeof(t));
+  if (groups) {
+    if (!bufs) return fail(AW_EINVAL, "aw_set_data: no buffers");
+    if (max_contacts < 1 || max_contacts > AW_DATA_MAX_CONTACTS)
+      return fail(AW_EINVAL, "aw_set_data: max_contacts must be 1..128 (the wide tier's contact storage)");
+    if ((groups & AW_DATA_KIN) && !(bufs->xpos && bufs->xquat && bufs->site_xpos))
+      return fail(AW_EINVAL, "aw_set_data: AW_DATA_KIN needs xpos, xquat and site_xpos");
+    if ((groups & AW_DATA_DYN) && !(bufs->qacc && bufs->qfrc_constraint && bufs->counts))
+      return fail(AW_EINVAL, "aw_set_data: AW_DATA_DYN needs qacc, qfrc_constraint and counts");
+    if ((groups & AW_DATA_CONTACT) && !bufs->contact) return fail(AW_EINVAL, "aw_set_data: AW_DATA_CONTACT needs contact");
+    if ((groups & AW_DATA_CONTACT) && ((uintptr_t)bufs->contact & 15))
+      return fail(AW_EINVAL, "aw_set_data: contact must be 16-byte aligned");
+    t.groups = groups;
+    t.max_contacts = max_contacts;
+    // only the requested groups' pointers reach the device: the others are never dereferenced
+    if (groups & AW_DATA_KIN) { t.xpos = bufs->xpos; t.xquat = bufs->xquat; t.site_xpos = bufs->site_xpos; }
+    if (groups & AW_DATA_DYN) { t.qacc = bufs->qacc; t.qfrc_constraint = bufs->qfrc_constraint; t.counts = bufs->counts; }
+    if (groups & AW_DATA_CONTACT) t.contact = (MRec*)bufs->contact;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // queued launches read the old table
+  HIPCHK(hipMemcpy(h->ddata, &t, offsetof(DataTab, geom_id), hipMemcpyHostToDevice));
+  h->data_groups = groups;
   return AW_OK;
 }
 

@@ -280,7 +280,9 @@ constexpr int COL_W = 8;      // colour record: rgb alpha specular 128*shininess
   X(int, tint_entry, MAXTINT) X(int, tint_chan, MAXTINT) X(int, tint_slot, MAXTINT)               \
   X(float, tint_scale, MAXTINT)                                                                  \
   /* the handle's sensor block (SensTab below), a device allocation of its own */                 \
-  X(const SensTab*, sens, 1)
+  X(const SensTab*, sens, 1)                                                                      \
+  /* the handle's mjData output block (DataTab below), a device allocation of its own */          \
+  X(const DataTab*, data, 1)
 
 // a 16-byte record of four floats (one LDS or global access)
 typedef float MRec __attribute__((ext_vector_type(4)));
@@ -300,6 +302,21 @@ struct SensTab {
   int site_type[MAXS];
   float site_size[MAXS * 3];
   int act_dof[MAXU];
+};
+
+// Batched mjData views (aw_solver.h stage_data), read only by the kernels that write them: the
+// groups selected by aw_set_data (AW_DATA_* bits, 0: off), the contact capacity K = max_contacts, the
+// caller's device buffers -- xpos [N][nbody][3], xquat [N][nbody][4], site_xpos [N][nsite][3], qacc and
+// qfrc_constraint [N][nv], counts int32 [N][4], contact [N][K] records of AW_CONTACT_DWORDS dwords --
+// and the model geom id of each collidable geom (the kernels index the compact list).  A device
+// block of its own like SensTab, allocated after it and reached through MData::data, the model
+// table's new last 8 bytes: nothing that existed before moves.
+struct DataTab {
+  int groups, max_contacts;
+  float *xpos, *xquat, *site_xpos, *qacc, *qfrc_constraint;
+  int* counts;
+  MRec* contact;
+  int geom_id[MAXG];
 };
 
 struct MData {
@@ -334,6 +351,7 @@ template <class T> AW_DEV gp_t<T> gmp(T* p) { return (gp_t<T>)p; }
 // the handle's sensor block, read like the model table (constant address space: uniform reads are
 // scalar loads); read-only for the life of a launch
 #define SENSTAB() ((const __attribute__((address_space(AW_MD_AS)))::aw::SensTab*)MD(sens, 0))
+#define DATATAB() ((const __attribute__((address_space(AW_MD_AS)))::aw::DataTab*)MD(data, 0))
 // per-env I/O (state, actions, params, obs, episode bookkeeping): device-global like the model
 // table, so read and written through global pointers too (AW_IO_GLOBAL; 0 restores generic
 // pointers, whose flat loads also hold lgkmcnt)

@@ -1532,4 +1532,81 @@ AW_DEV void stage_sensors(const DModel& m, Env& s, int lane, int env) {
   wsync();
 }
 
+// Batched mjData views (aw_set_data): what sim.data holds after the forward that just ran, written
+// straight from LDS and registers to the caller's device buffers (DataTab) -- nothing is staged in
+// Env.  Runs wherever stage_sensors runs.  Groups (uniform per launch):
+//   AW_DATA_KIN      xpos [nbody][3], xquat [nbody][4], site_xpos [nsite][3] of env's rows
+//   AW_DATA_DYN      qacc, qfrc_constraint [nv] (the forward's lane-local dof registers) and counts
+//                    int32 [4] = ncon, nefc, Newton iterations, noslip sweeps
+//   AW_DATA_CONTACT  the first min(ncon, K) contacts in the kernel's (= mj_collision's) order, one
+//                    64-byte record each; records past them are not touched.  Footprint 64 K bytes
+//                    per env: 134 MB at 65 536 envs with K = 32 (DAPG grasps reach 12 contacts).
+// Contact record, AW_CONTACT_DWORDS = 16 dwords (include/adroit_wave.h):
+//   float dist, pos[3] | normal[3] (unit, geom1 -> geom2), force[0] | force[1], force[2], torsion, mu
+//   | int32 geom1, geom2 (model geom ids), dim, efc_address
+// force is mj_contactForce's in the contact frame (normal, then the two tangents of
+// make_frame(normal)) from efc_force after noslip: condim 1 the row's force; pyramidal, normal = the
+// sum of the 2 (dim - 1) edge forces (summed in stage_touch's order: the same bits) and component i =
+// (f[2i-2] - f[2i-1]) mu[i-1], condim 4's third component in `torsion` (the rolling components of
+// condim 6 have no slot).  mu is the sliding friction.  A contact without rows (con_efc < 0) has zero
+// force and efc_address -1.  One lane per contact, four dwordx4 stores; consecutive contacts are
+// consecutive records, so a wave's stores coalesce.
+AW_DEV void stage_data(const DModel& m, Env& s, int lane, int env, float qacc, float qfrc_con) {
+  const auto t = DATATAB();
+  const int groups = t->groups;
+  if (groups & AW_DATA_KIN) {
+    const int nb = m.nbody, ns = m.nsite;
+    float* xp = t->xpos + (size_t)env * (3 * nb);
+    float* xq = t->xquat + (size_t)env * (4 * nb);
+    float* sx = t->site_xpos + (size_t)env * (3 * ns);
+    for (int i = lane; i < 3 * nb; i += 64) GOUT(xp)[i] = (&s.xpos[0][0])[i];
+    for (int i = lane; i < 4 * nb; i += 64) GOUT(xq)[i] = (&s.xquat[0][0])[i];
+    for (int i = lane; i < 3 * ns; i += 64) GOUT(sx)[i] = (&s.sxpos[0][0])[i];
+  }
+  if (groups & AW_DATA_DYN) {
+    if (lane < m.nv) {
+      GOUT(t->qacc)[(size_t)env * m.nv + lane] = qacc;
+      GOUT(t->qfrc_constraint)[(size_t)env * m.nv + lane] = qfrc_con;
+    }
+    if (lane < 4) {
+      // it_newton carries the exit reason in its thousands (aw_forward_dump)
+      const int v = lane == 0 ? s.ncon : lane == 1 ? s.nefc : lane == 2 ? s.it_newton % 1000 : s.it_noslip;
+      GOUT(t->counts)[(size_t)env * 4 + lane] = v;
+    }
+  }
+  if (groups & AW_DATA_CONTACT) {
+    const int K = t->max_contacts;
+    const int nw = s.ncon < K ? s.ncon : K;
+    MRec* rec = t->contact + (size_t)env * K * (AW_CONTACT_DWORDS / 4);
+#pragma unroll
+    for (int h = 0; h < NCH; h++) {
+      const int c = lane + 64 * h;
+      if (c < nw) {
+        const int pr = s.con_pair[c], adr = s.con_efc[c], dim = MD(cp_condim, pr);
+        float nrm[3];
+        copy3(nrm, s.con_nrm[c]);
+        normalize3(nrm);
+        float f0 = 0.f, f1 = 0.f, f2 = 0.f, tors = 0.f;
+        if (adr >= 0) {
+          if (dim == 1) {
+            f0 = s.efc_force[adr];
+          } else {
+            for (int j = 0; j < 2 * (dim - 1); j++) f0 += s.efc_force[adr + j];
+            f1 = (s.efc_force[adr] - s.efc_force[adr + 1]) * MD(cp_friction, 5 * pr);
+            if (dim > 2) f2 = (s.efc_force[adr + 2] - s.efc_force[adr + 3]) * MD(cp_friction, 5 * pr + 1);
+            if (dim > 3) tors = (s.efc_force[adr + 4] - s.efc_force[adr + 5]) * MD(cp_friction, 5 * pr + 2);
+          }
+        }
+        const int g1 = t->geom_id[MD(cp_g1, pr)], g2 = t->geom_id[MD(cp_g2, pr)];
+        const auto r = GOUT(rec + (size_t)c * (AW_CONTACT_DWORDS / 4));
+        r[0] = MRec{s.con_dist[c], s.con_pos[c][0], s.con_pos[c][1], s.con_pos[c][2]};
+        r[1] = MRec{nrm[0], nrm[1], nrm[2], f0};
+        r[2] = MRec{f1, f2, tors, MD(cp_friction, 5 * pr)};
+        r[3] = MRec{__int_as_float(g1), __int_as_float(g2), __int_as_float(dim), __int_as_float(adr < 0 ? -1 : adr)};
+      }
+    }
+  }
+  wsync();
+}
+
 }  // namespace aw

@@ -56,8 +56,14 @@ class AdroitVecEnv:
     """``num_envs`` envs of ``env_id`` on GPU ``device``; every buffer stays in HBM."""
 
     def __init__(self, env_id: str, num_envs: int, device: int = 0, variation_type: Optional[str] = None,
-                 seed: int = 1, autoreset: bool = True, sensors: bool = False):
+                 seed: int = 1, autoreset: bool = True, sensors: bool = False, data=False,
+                 max_contacts: int = 32):
         import torch
+        # batched sim.data views (mj_envs_amd/data.py), opt-in: False, True (every group) or group names
+        # out of "kin", "dyn", "contact"; checked before anything touches the GPU
+        self._data_groups = _native.data_groups(data)
+        if self._data_groups and not 1 <= int(max_contacts) <= _native.AW_DATA_MAX_CONTACTS:
+            raise ValueError(f"max_contacts must be 1..{_native.AW_DATA_MAX_CONTACTS}, not {max_contacts}")
         self.env_id = env_id
         self.spec = TASKS[env_id]
         self.model = attach_task(load_model(env_id), env_id, variation_type)
@@ -91,6 +97,20 @@ class AdroitVecEnv:
             self.sensor_names = [self.model.names["sensor"][i] for i in order]
             self.sensor_types = self.model.arrays["sensor_type"][order].astype(np.int32)   # mjcf.SENS_*
             self._touch_cols = torch.as_tensor(np.flatnonzero(self.sensor_types == SENS_TOUCH), device=s.torch_device)
+        # the kernels write the views' tensors in place on every step / reset / set_state: no copy
+        self._data = None
+        if self._data_groups:
+            from .data import DataViews
+            self._data = DataViews(self.model, s, self._data_groups, int(max_contacts))
+
+    @property
+    def data(self):
+        """``sim.data`` of every env after the last step / reset / set_state (mj_envs_amd/data.py
+        DataViews): body_xpos, body_xquat, site_xpos, qacc, qfrc_constraint, ncon, nefc,
+        solver_iter, noslip_iter and contact.* as torch views of device memory"""
+        if self._data is None:
+            raise AttributeError("data: this env was created with data=False")
+        return self._data
 
     def _no_sensors(self, what):
         raise AttributeError(f"{what}: this env was created with sensors=False")
@@ -246,14 +266,15 @@ class _AdroitEnv(_reference_base()):
 
     def __init__(self, render_mode=None, width: int = 64, height: int = 64, is_headless: bool = True,
                  variation_type: Optional[str] = None, device: int = 0, seed: Optional[int] = None,
-                 sensors: bool = False):
+                 sensors: bool = False, data=False, max_contacts: int = 32):
         import torch
         self.render_mode, self.width, self.height = render_mode, width, height
         self.is_headless = is_headless
         self.variation_type = variation_type
         self.observer = None            # the camera record once mj_viewer_headless_setup() ran
         self.vec = AdroitVecEnv(self.env_id, 1, device=device, variation_type=variation_type,
-                                seed=1, autoreset=False, sensors=sensors)
+                                seed=1, autoreset=False, sensors=sensors, data=data,
+                                max_contacts=max_contacts)
         self.vec._facade = self         # camera flags (pen's use_aerial_view) of this facade
         self.model = self.vec.model
         self.frame_skip = self.vec.frame_skip
@@ -304,6 +325,14 @@ class _AdroitEnv(_reference_base()):
         """``self.data.sensordata`` of the reference: float64 [nsensordata] of the last step / reset /
         set_env_state (needs ``sensors=True``)"""
         return self.vec.sensordata[0].cpu().numpy().astype(np.float64)
+
+    @property
+    def data(self):
+        """``self.data`` of the reference (``sim.data``) after the last step / reset / set_env_state:
+        float64 numpy copies of body_xpos, body_xquat, site_xpos, qacc, qfrc_constraint, ncon, nefc,
+        solver_iter, noslip_iter and contact.* cut to ncon (needs ``data=True`` or group names)"""
+        from .data import EnvData
+        return EnvData(self.vec.data)
 
     def _params(self) -> np.ndarray:
         return self.vec.get_state()["params"][0].cpu().numpy().astype(np.float64)

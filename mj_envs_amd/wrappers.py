@@ -236,11 +236,15 @@ def make_env(config, num_envs: int = 1, device: int = 0):
     state), ``config.nogui`` (False: the GUI wrapper, state tensors, no pixels); optional
     ``config.pixel_mode``: ``"depth"`` (default) or ``"rgb"`` (colour pixels, 2x2 rays per pixel:
     the reference's resized frame); optional ``config.sensors``: MuJoCo's sensordata in
-    ``info["sensordata"]`` of every step (``AdroitVecEnv(sensors=True)``)."""
+    ``info["sensordata"]`` of every step (``AdroitVecEnv(sensors=True)``); optional ``config.data``
+    (True or group names) and ``config.max_contacts``: the batched ``sim.data`` views in ``env.data``
+    (``AdroitVecEnv(data=...)``)."""
     env = AdroitVecEnv(config.env_name, num_envs, device=device,
                        variation_type=getattr(config, "variation_type", None),
                        seed=int(getattr(config, "seed", 1) or 1),
-                       sensors=bool(getattr(config, "sensors", False)))
+                       sensors=bool(getattr(config, "sensors", False)),
+                       data=getattr(config, "data", False) or False,
+                       max_contacts=int(getattr(config, "max_contacts", 32) or 32))
     rk = dict(width=64, height=64)
     mode = getattr(config, "pixel_mode", "depth") or "depth"
     if mode == "rgb":
