@@ -74,7 +74,10 @@ enum {
 };
 
 /* model table = Model.to_blob() of mj_envs_amd/mjcf.py with the task block attached
- * (mj_envs_amd/tasks.py attach_task).  Allocates state for n_envs envs on `device`. */
+ * (mj_envs_amd/tasks.py attach_task).  Allocates state for n_envs envs on `device`.
+ * The table is not trusted (mj_envs_amd/csrc/aw_model_host.h): an entry that is missing or whose
+ * length does not follow from the table's dims, or an object id out of range, is AW_EBLOB; a
+ * well-formed model beyond the kernels' capacities or features is AW_EUNSUPPORTED. */
 int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle** out);
 int aw_destroy(aw_handle* h);
 int aw_dims(const aw_handle* h, int* dims /* [AW_NDIMS] */);

@@ -36,8 +36,10 @@ static inline int aw_blob_find(const void* blob, size_t nbytes, const char* name
     int32_t hdr[3];
     memcpy(hdr, p + 32, 12);
     size_t esz = hdr[0] == 1 ? 4 : 8;
-    size_t bytes = (size_t)hdr[1] * (size_t)hdr[2] * esz;
-    if (p + 44 + bytes > end) return 0;
+    if (hdr[1] < 0 || hdr[2] < 0) return 0;
+    size_t cnt = (size_t)hdr[1] * (size_t)hdr[2];   /* < 2^62: no overflow */
+    if (cnt > ((size_t)(end - p) - 44) / esz) return 0;
+    size_t bytes = cnt * esz;
     if (strncmp(p, name, 32) == 0) {
       out->name = p;
       out->kind = hdr[0];

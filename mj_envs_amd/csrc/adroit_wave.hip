@@ -4,11 +4,13 @@
 // (forward + Euler) and the task layer for every env; the per-env working set stays in LDS /
 // VGPRs for the whole launch, so HBM traffic is the compulsory state + action + obs bytes.
 //
-// Build split (__graft_entry__.py): the library is this file compiled five times in parallel and
-// linked -- once per task with -DAW_TASK_TU=<task> (that task's kernels and its launcher table,
-// task_ops<TASK>) and once with -DAW_API_TU (the C-ABI and the task-independent kernels, no
+// Build split (__graft_entry__.py): the library is this file compiled as nine translation units in
+// parallel and linked -- per task once with -DAW_TASK_TU=<task> (that task's fast-tier kernels and
+// its launcher table, task_ops<TASK>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier's,
+// wide_ops<TASK>), and once with -DAW_API_TU (the C-ABI and the task-independent kernels, no
 // per-task instantiation).  A plain compile of the file (diagnostic builds: -DAW_ONLY_TASK,
-// -DAW_STAGE_PROF) is the whole library in one translation unit.
+// -DAW_STAGE_PROF) is the fast tier and the C-ABI in one translation unit.
+// The model table -> device tables builder is host-only code of its own: aw_model_host.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -17,6 +19,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/adroit_wave.h"
@@ -26,6 +29,7 @@
 #include "aw_dynamics.h"
 #include "aw_render.h"
 #ifndef AW_TASK_TU
+#include "aw_model_host.h"
 #include "aw_policy.h"
 #endif
 #include "aw_solver.h"
@@ -1187,48 +1191,16 @@ thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(AW_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
-struct Blob {
-  const void* p; size_t n;
-  bool has(const char* name) const { aw_blob_entry e; return aw_blob_find(p, n, name, &e); }
-  std::vector<double> f(const char* name) const {
-    aw_blob_entry e;
-    std::vector<double> out;
-    if (!aw_blob_find(p, n, name, &e)) return out;
-    size_t cnt = (size_t)e.rows * e.cols;
-    out.resize(cnt);
-    const char* d = (const char*)e.data;
-    for (size_t i = 0; i < cnt; i++) {
-      if (e.kind == 0) { double v; memcpy(&v, d + 8 * i, 8); out[i] = v; }
-      else { int32_t v; memcpy(&v, d + 4 * i, 4); out[i] = v; }
-    }
-    return out;
-  }
-  std::vector<int> i(const char* name) const {
-    std::vector<double> v = f(name);
-    return std::vector<int>(v.begin(), v.end());
-  }
-  int dim(const char* name, int dflt = -1) const { return aw_blob_dim(p, n, name, dflt); }
-  double opt(const char* name, double dflt) const { return aw_blob_opt(p, n, name, dflt); }
-};
-
-template <class T, size_t N, class U>
-bool put_arr(T (&dst)[N], const std::vector<U>& v) {
-  if (v.size() > N) return false;
-  for (size_t i = 0; i < v.size(); i++) dst[i] = (T)v[i];
-  return true;
-}
-#define PUT(name, ...)                                                                        \
-  do {                                                                                        \
-    if (!put_arr(md.name, __VA_ARGS__)) return fail(AW_EUNSUPPORTED, "model field " #name " exceeds kernel capacity"); \
-  } while (0)
-
-std::vector<float> tof(const std::vector<double>& v) { return std::vector<float>(v.begin(), v.end()); }
 }  // namespace
 
 #endif  // AW_TASK_TU
 
+struct TaskOps;
+struct WideOps;
 struct aw_handle {
   int device, nenv, NV;
+  const TaskOps* ops = nullptr;   // the launchers of the model's task, fast and wide tier (aw_create)
+  const WideOps* wide = nullptr;
   DModel m;
   DState st;
   void* dmodel = nullptr;
@@ -1270,430 +1242,29 @@ static int upload_header(aw_handle* h) {
   HIPCHK(hipMemcpy((DModel*)h->dmhdr_wide + 1, &h->st, sizeof(DState), hipMemcpyHostToDevice));
   return AW_OK;
 }
-
-static int build_model(const Blob& B, DModel& m, MData& md, SensTab& sens, DataTab& data) {
-  memset(&m, 0, sizeof(m));
-  int nq = B.dim("nq"), nv = B.dim("nv"), nu = B.dim("nu"), nbody = B.dim("nbody"), njnt = B.dim("njnt");
-  int ngeom_all = B.dim("ngeom"), nsite = B.dim("nsite"), ntendon = B.dim("ntendon");
-  int npair = B.dim("npair"), ncand = B.dim("ncand"), nsensor = B.dim("nsensor");
-  if (nq < 0 || nv < 0 || nbody < 0 || B.dim("task_kind") < 0) return fail(AW_EBLOB, "model table lacks dims / task block");
-  if (nq != nv || njnt != nv) return fail(AW_EUNSUPPORTED, "only hinge/slide joints are supported");
-  if (nv > MAXV || nbody > MAXB || nsite > MAXS || ntendon > MAXT || nu > MAXU)
-    return fail(AW_EUNSUPPORTED, "model exceeds kernel capacity");
-  m.nq = nq; m.nv = nv; m.nu = nu; m.nbody = nbody; m.njnt = njnt; m.nsite = nsite; m.ntendon = ntendon;
-  m.timestep = (float)B.opt("timestep", 0.002);
-  m.gravity[0] = (float)B.opt("gravity_x", 0); m.gravity[1] = (float)B.opt("gravity_y", 0);
-  m.gravity[2] = (float)B.opt("gravity_z", -9.81);
-  m.iterations = (int)B.opt("iterations", 100);
-  m.tolerance = (float)B.opt("tolerance", 1e-8);
-  m.noslip_iterations = (int)B.opt("noslip_iterations", 0);
-  m.noslip_tolerance = (float)B.opt("noslip_tolerance", 1e-6);
-  m.mpr_tolerance = (float)B.opt("mpr_tolerance", 1e-6);
-  m.mpr_iterations = (int)B.opt("mpr_iterations", 50);
-  m.mpr_tolerance64 = B.opt("mpr_tolerance", 1e-6);
-  m.meaninertia = (float)B.opt("meaninertia", 1);
-  // pyramidal cones only: R = max(mjMINVAL, (1 - imp) / imp * diagApprox) per edge row, diagApprox =
-  // invweight_tran + friction^2 * invweight_(tran|rot); impratio (the elliptic cones' friction /
-  // normal impedance ratio) is restated only at its default 1, where it is the identity
-  if (B.opt("impratio", 1) != 1.0) return fail(AW_EUNSUPPORTED, "impratio != 1");
-  m.pen_length = (float)B.opt("task_pen_length", 1);
-  m.tar_length = (float)B.opt("task_tar_length", 1);
-  m.task_kind = B.dim("task_kind"); m.frame_skip = B.dim("task_frame_skip", 1);
-  m.horizon = B.dim("task_horizon", 0); m.obs_dim = B.dim("task_obs_dim", 0);
-  // the observation is assembled in the row buffer (write_obs): it must fit the fast tier's
-  if (m.obs_dim < 0 || m.obs_dim > 64 * FAST_NRL) return fail(AW_EUNSUPPORTED, "observation larger than the row buffer");
-  m.success_steps = B.dim("task_success_steps", 25);
-  m.nparam = B.dim("task_nparam", 0); m.variation = B.dim("task_variation", 0);
-  if (m.nparam > MAXP) return fail(AW_EUNSUPPORTED, "too many per-env params");
-  m.disableflags = 0;
-  m.fault_flrow = -1;
-
-  std::vector<int> parent = B.i("body_parentid"), rootid = B.i("body_rootid"), dofnum = B.i("body_dofnum"),
-                   dofadr = B.i("body_dofadr");
-  for (int b = 0; b < nbody; b++)
-    if (dofnum[b] > MAXJB) return fail(AW_EUNSUPPORTED, "more than MAXJB joints in one body");
-  // subtree ends (DFS order), levels, dof masks
-  std::vector<int> send(nbody), depth(nbody, 0);
-  for (int b = 0; b < nbody; b++) send[b] = b + 1;
-  for (int b = nbody - 1; b > 0; b--) send[parent[b]] = std::max(send[parent[b]], send[b]);
-  for (int b = 1; b < nbody; b++) depth[b] = depth[parent[b]] + 1;
-  int nlev = 0;
-  for (int b = 0; b < nbody; b++) nlev = std::max(nlev, depth[b] + 1);
-  if (nlev > MAXLEV) return fail(AW_EUNSUPPORTED, "tree too deep");
-  std::vector<int> lstart(nlev + 1, 0), lbody;
-  for (int l = 0; l < nlev; l++) {
-    lstart[l] = (int)lbody.size();
-    for (int b = 0; b < nbody; b++)
-      if (depth[b] == l) lbody.push_back(b);
-  }
-  lstart[nlev] = (int)lbody.size();
-  m.nlevel = nlev;
-  std::vector<int> dparent = B.i("dof_parentid");
-  std::vector<unsigned long long> bmask(nbody, 0), amask(nv, 0);
-  for (int b = 1; b < nbody; b++) {
-    int a = b;
-    while (a > 0) {
-      for (int k = 0; k < dofnum[a]; k++) bmask[b] |= 1ull << (dofadr[a] + k);
-      a = parent[a];
-    }
-  }
-  for (int j = 0; j < nv; j++)
-    for (int a = dparent[j]; a >= 0; a = dparent[a]) amask[j] |= 1ull << a;
-
-  PUT(body_parentid, parent); PUT(body_rootid, rootid); PUT(body_dofnum, dofnum);
-  PUT(body_dofadr, dofadr); PUT(body_depth, depth); PUT(body_subtree_end, send); PUT(level_start, lstart);
-  PUT(level_body, lbody);
-  PUT(body_pos, tof(B.f("body_pos"))); PUT(body_quat, tof(B.f("body_quat")));
-  PUT(body_ipos, tof(B.f("body_ipos"))); PUT(body_iquat, tof(B.f("body_iquat")));
-  PUT(body_mass, tof(B.f("body_mass"))); PUT(body_inertia, tof(B.f("body_inertia")));
-  PUT(body_invweight0, tof(B.f("body_invweight0")));
-  PUT(body_subtreemass, tof(B.f("body_subtreemass")));
-  PUT(body_dofmask, bmask);
-  PUT(body_pos64, B.f("body_pos")); PUT(body_quat64, B.f("body_quat"));
-  PUT(jnt_pos64, B.f("jnt_pos")); PUT(jnt_axis64, B.f("jnt_axis"));
-
-  std::vector<int> jtype = B.i("jnt_type");
-  for (int t : jtype) if (t != JNT_HINGE && t != JNT_SLIDE) return fail(AW_EUNSUPPORTED, "joint type");
-  PUT(jnt_type, jtype); PUT(jnt_bodyid, B.i("jnt_bodyid")); PUT(jnt_limited, B.i("jnt_limited"));
-  PUT(jnt_pos, tof(B.f("jnt_pos"))); PUT(jnt_axis, tof(B.f("jnt_axis")));
-  PUT(jnt_range, tof(B.f("jnt_range"))); PUT(jnt_margin, tof(B.f("jnt_margin")));
-  PUT(jnt_solref, tof(B.f("jnt_solref"))); PUT(jnt_solimp, tof(B.f("jnt_solimp")));
-  PUT(jnt_range64, B.f("jnt_range")); PUT(jnt_margin64, B.f("jnt_margin"));
-
-  // actuators (joint transmission, one per dof)
-  std::vector<int> trn = B.i("actuator_trnid");
-  std::vector<int> dact(nv, -1);
-  for (int u = 0; u < nu; u++) {
-    if (dact[trn[u]] >= 0) return fail(AW_EUNSUPPORTED, "two actuators on one joint");
-    dact[trn[u]] = u;
-  }
-  std::vector<double> floss = B.f("dof_frictionloss");
-  std::vector<int> fl_dof, fl_row(nv, -1);
-  for (int j = 0; j < nv; j++)
-    if (floss[j] > 0) { fl_row[j] = (int)fl_dof.size(); fl_dof.push_back(j); }
-  m.nfl = (int)fl_dof.size();
-  PUT(dof_bodyid, B.i("dof_bodyid")); PUT(dof_act, dact); PUT(fl_dof, fl_dof);
-  PUT(fl_row, fl_row); PUT(dof_ancmask, amask);
-  PUT(dof_armature, tof(B.f("dof_armature"))); PUT(dof_damping, tof(B.f("dof_damping")));
-  PUT(dof_frictionloss, tof(floss)); PUT(dof_invweight0, tof(B.f("dof_invweight0")));
-  PUT(dof_solref, tof(B.f("dof_solref"))); PUT(dof_solimp, tof(B.f("dof_solimp")));
-
-  // compact collidable geoms
-  std::vector<int> gtype = B.i("geom_type"), gcon = B.i("geom_contype"), gaff = B.i("geom_conaffinity"),
-                   gbody = B.i("geom_bodyid");
-  std::vector<double> gpos = B.f("geom_pos"), gquat = B.f("geom_quat"), gsize = B.f("geom_size"),
-                      grb = B.f("geom_rbound");
-  std::vector<int> gmap(ngeom_all, -1), ctype, cbody;
-  std::vector<float> cpos, cquat, csize, crb;
-  std::vector<double> cpos64, cquat64, csize64;
-  for (int g = 0; g < ngeom_all; g++) {
-    if (gtype[g] == 7 || (gcon[g] == 0 && gaff[g] == 0)) continue;
-    gmap[g] = (int)ctype.size();
-    ctype.push_back(gtype[g]); cbody.push_back(gbody[g]);
-    for (int k = 0; k < 3; k++) { cpos.push_back((float)gpos[3 * g + k]); csize.push_back((float)gsize[3 * g + k]); }
-    for (int k = 0; k < 4; k++) cquat.push_back((float)gquat[4 * g + k]);
-    for (int k = 0; k < 3; k++) { cpos64.push_back(gpos[3 * g + k]); csize64.push_back(gsize[3 * g + k]); }
-    for (int k = 0; k < 4; k++) cquat64.push_back(gquat[4 * g + k]);
-    crb.push_back((float)grb[g]);
-  }
-  PUT(geom_pos64, cpos64); PUT(geom_quat64, cquat64); PUT(geom_size64, csize64);
-  m.ngeom = (int)ctype.size();
-  if (m.ngeom > MAXG) return fail(AW_EUNSUPPORTED, "too many collidable geoms");
-  memset(&data, 0, sizeof(data));   // stage_data's table: off, and the model geom id of each collidable geom
-  for (int g = 0; g < ngeom_all; g++)
-    if (gmap[g] >= 0) data.geom_id[gmap[g]] = g;
-  PUT(geom_type, ctype); PUT(geom_bodyid, cbody); PUT(geom_pos, cpos);
-  PUT(geom_quat, cquat); PUT(geom_size, csize); PUT(geom_rbound, crb);
-
-  PUT(site_bodyid, B.i("site_bodyid")); PUT(site_pos, tof(B.f("site_pos")));
-  PUT(site_quat, tof(B.f("site_quat")));
-
-  // tendons: fixed, <= 2 joints
-  std::vector<int> tadr = B.i("tendon_adr"), tnum = B.i("tendon_num"), wj = B.i("wrap_jnt");
-  std::vector<double> wc = B.f("wrap_coef"), tfl = B.f("tendon_frictionloss");
-  std::vector<int> d0(ntendon), d1(ntendon);
-  std::vector<float> c0(ntendon), c1(ntendon);
-  for (int t = 0; t < ntendon; t++) {
-    if (tnum[t] < 1 || tnum[t] > 2) return fail(AW_EUNSUPPORTED, "tendon with != 1..2 joints");
-    if (tfl[t] > 0) return fail(AW_EUNSUPPORTED, "tendon frictionloss");
-    d0[t] = wj[tadr[t]]; c0[t] = (float)wc[tadr[t]];
-    d1[t] = tnum[t] > 1 ? wj[tadr[t] + 1] : -1; c1[t] = tnum[t] > 1 ? (float)wc[tadr[t] + 1] : 0.f;
-  }
-  PUT(ten_d0, d0); PUT(ten_d1, d1); PUT(ten_limited, B.i("tendon_limited"));
-  PUT(ten_c0, c0); PUT(ten_c1, c1); PUT(ten_range, tof(B.f("tendon_range")));
-  PUT(ten_margin, tof(B.f("tendon_margin"))); PUT(ten_solref, tof(B.f("tendon_solref")));
-  PUT(ten_solimp, tof(B.f("tendon_solimp"))); PUT(ten_invweight0, tof(B.f("tendon_invweight0")));
-  PUT(ten_range64, B.f("tendon_range")); PUT(ten_margin64, B.f("tendon_margin"));
-  {
-    std::vector<double> a0(ntendon), a1(ntendon);
-    for (int t = 0; t < ntendon; t++) { a0[t] = wc[tadr[t]]; a1[t] = tnum[t] > 1 ? wc[tadr[t] + 1] : 0.0; }
-    PUT(ten_c0_64, a0); PUT(ten_c1_64, a1);
-  }
-
-  std::vector<double> gain = B.f("actuator_gainprm");
-  std::vector<float> g0(nu);
-  for (int u = 0; u < nu; u++) g0[u] = (float)gain[3 * u];
-  PUT(act_ctrllimited, B.i("actuator_ctrllimited")); PUT(act_forcelimited, B.i("actuator_forcelimited"));
-  PUT(act_gear, tof(B.f("actuator_gear"))); PUT(act_gain, g0);
-  PUT(act_bias, tof(B.f("actuator_biasprm"))); PUT(act_ctrlrange, tof(B.f("actuator_ctrlrange")));
-  PUT(act_forcerange, tof(B.f("actuator_forcerange")));
-
-  // unified pair list: explicit pairs (own params), then candidates (params mixed here in fp64,
-  // mj_contactParam with equal priorities)
-  std::vector<int> pg1, pg2, pcd;
-  std::vector<float> pfr, psr, psi, pmg, pgp;
-  std::vector<double> pmg64;
-  {
-    std::vector<int> e1 = B.i("pair_geom1"), e2 = B.i("pair_geom2"), ecd = B.i("pair_condim");
-    std::vector<double> efr = B.f("pair_friction"), esr = B.f("pair_solref"), esi = B.f("pair_solimp"),
-                        emg = B.f("pair_margin"), egp = B.f("pair_gap");
-    for (int p = 0; p < npair; p++) {
-      if (gmap[e1[p]] < 0 || gmap[e2[p]] < 0) return fail(AW_EUNSUPPORTED, "pair with a visual geom");
-      pg1.push_back(gmap[e1[p]]); pg2.push_back(gmap[e2[p]]); pcd.push_back(ecd[p]);
-      for (int k = 0; k < 5; k++) pfr.push_back((float)efr[5 * p + k]);
-      for (int k = 0; k < 2; k++) psr.push_back((float)esr[2 * p + k]);
-      for (int k = 0; k < 5; k++) psi.push_back((float)esi[5 * p + k]);
-      pmg.push_back((float)emg[p]); pgp.push_back((float)egp[p]); pmg64.push_back(emg[p]);
-    }
-    std::vector<int> c1v = B.i("cand_geom1"), c2v = B.i("cand_geom2"), gcd = B.i("geom_condim");
-    std::vector<double> gfr = B.f("geom_friction"), gsm = B.f("geom_solmix"), gsr = B.f("geom_solref"),
-                        gsi = B.f("geom_solimp"), gmg = B.f("geom_margin"), ggp = B.f("geom_gap");
-    for (int c = 0; c < ncand; c++) {
-      int a = c1v[c], b = c2v[c];
-      pg1.push_back(gmap[a]); pg2.push_back(gmap[b]);
-      pcd.push_back(std::max(gcd[a], gcd[b]));
-      double s1 = gsm[a], s2 = gsm[b], mix;
-      if (s1 >= 1e-15 && s2 >= 1e-15) mix = s1 / (s1 + s2);
-      else if (s1 < 1e-15 && s2 < 1e-15) mix = 0.5;
-      else mix = s1 < 1e-15 ? 0.0 : 1.0;
-      double f0 = std::max(gfr[3 * a], gfr[3 * b]), f1 = std::max(gfr[3 * a + 1], gfr[3 * b + 1]),
-             f2 = std::max(gfr[3 * a + 2], gfr[3 * b + 2]);
-      double fr[5] = {f0, f0, f1, f2, f2};
-      for (int k = 0; k < 5; k++) pfr.push_back((float)fr[k]);
-      for (int k = 0; k < 2; k++) psr.push_back((float)(mix * gsr[2 * a + k] + (1 - mix) * gsr[2 * b + k]));
-      for (int k = 0; k < 5; k++) psi.push_back((float)(mix * gsi[5 * a + k] + (1 - mix) * gsi[5 * b + k]));
-      pmg.push_back((float)std::max(gmg[a], gmg[b])); pgp.push_back((float)std::max(ggp[a], ggp[b]));
-      pmg64.push_back(std::max(gmg[a], gmg[b]));
-    }
-  }
-  m.npairall = (int)pg1.size();
-  {
-    // collider class per pair (aw_collide.h collide_pair dispatch) and the broadphase radius
-    std::vector<int> pcls(m.npairall);
-    std::vector<float> prb(m.npairall);
-    int ccount[NCLASS] = {0, 0, 0, 0, 0};
-    for (int p = 0; p < m.npairall; p++) {
-      int a = pg1[p], b = pg2[p];
-      int ta = ctype[a], tb = ctype[b];
-      int lo = std::min(ta, tb), hi = std::max(ta, tb);
-      int c;
-      if (lo == GEOM_PLANE) c = 0;
-      else if (lo == GEOM_CYLINDER || hi == GEOM_CYLINDER) c = 4;
-      else if (hi == GEOM_BOX && lo == GEOM_BOX) c = 3;
-      else if (hi == GEOM_BOX) c = 2;
-      else c = 1;
-      pcls[p] = c;
-      ccount[c]++;
-      // plane pairs: -(1 + rbound of the other geom + margin) (< -1: the broadphase's plane test)
-      prb[p] = lo == GEOM_PLANE ? (float)(-1.0 - (double)crb[ta == GEOM_PLANE ? b : a] - (double)pmg[p])
-                                : (float)((double)crb[a] + (double)crb[b] + (double)pmg[p]);
-    }
-    m.cls_start[0] = 0;
-    for (int c = 0; c < NCLASS; c++) m.cls_start[c + 1] = m.cls_start[c] + ccount[c];
-    if (m.npairall > JL * VS * 2) return fail(AW_EUNSUPPORTED, "too many collision pairs");
-    PUT(cp_class, pcls); PUT(cp_rb, prb); PUT(cp_margin64, pmg64);
-    // per pair: the bodies whose fp64 frames its geometry needs (stage_kin64), with ancestors
-    // (every class: the sphere / capsule pairs' near-margin contacts are decided on fp64 frames too)
-    std::vector<unsigned long long> k64(m.npairall, 0ull);
-    for (int p = 0; p < m.npairall; p++)
-      for (int g : {pg1[p], pg2[p]})
-        for (int b = cbody[g]; b > 0; b = parent[b]) k64[p] |= 1ull << b;
-    PUT(cp_kin64, k64);
-    std::vector<int> ppack(m.npairall);
-    for (int p = 0; p < m.npairall; p++) ppack[p] = pcls[p] | (pg1[p] << 8) | (pg2[p] << 16);
-    PUT(cp_pack, ppack);
-  }
-  {
-    std::vector<double> iw = B.f("body_invweight0");
-    std::vector<float> ptran(pg1.size()), prot(pg1.size());
-    std::vector<int> pr1(pg1.size()), pr2(pg1.size());
-    std::vector<unsigned long long> pm1(pg1.size()), pm2(pg1.size());
-    for (size_t p = 0; p < pg1.size(); p++) {
-      const int b1 = cbody[pg1[p]], b2 = cbody[pg2[p]];
-      ptran[p] = (float)iw[2 * b1] + (float)iw[2 * b2];
-      prot[p] = (float)iw[2 * b1 + 1] + (float)iw[2 * b2 + 1];
-      pr1[p] = rootid[b1]; pr2[p] = rootid[b2];
-      pm1[p] = bmask[b1]; pm2[p] = bmask[b2];
-    }
-    PUT(cp_tran, ptran); PUT(cp_rot, prot); PUT(cp_root1, pr1); PUT(cp_root2, pr2);
-    PUT(cp_mask1, pm1); PUT(cp_mask2, pm2);
-  }
-  PUT(cp_g1, pg1); PUT(cp_g2, pg2); PUT(cp_condim, pcd); PUT(cp_friction, pfr);
-  PUT(cp_solref, psr); PUT(cp_solimp, psi); PUT(cp_margin, pmg); PUT(cp_gap, pgp);
-
-  // task block
-  std::vector<int> tidx = B.i("task_idx"), pf = B.i("task_param_field"), po = B.i("task_param_obj"),
-                   pc = B.i("task_param_comp");
-  for (int p = 0; p < m.nparam; p++)
-    if (pf[p] == 4 || pf[p] == 5) {
-      if (gmap[po[p]] < 0) return fail(AW_EUNSUPPORTED, "param on a visual geom");
-      po[p] = gmap[po[p]];
-    }
-  // touch sensors read by the task (hammer: S_nail, task_idx[5] = its sensordata address)
-  std::vector<int> ts, ttype;
-  std::vector<float> tsize;
-  if (m.task_kind == 0 && tidx.size() > 5) {
-    std::vector<int> stype = B.i("sensor_type"), sobj = B.i("sensor_objid"), sadr = B.i("sensor_adr");
-    std::vector<int> sitetype = B.i("site_type");
-    std::vector<double> ssize = B.f("site_size");
-    for (int k = 0; k < nsensor; k++)
-      if (sadr[k] == tidx[5] && stype[k] == 0) {
-        ts.push_back(sobj[k]); ttype.push_back(sitetype[sobj[k]]);
-        for (int q = 0; q < 3; q++) tsize.push_back((float)ssize[3 * sobj[k] + q]);
-      }
-  }
-  m.ntouch = (int)ts.size();
-  PUT(touch_site, ts); PUT(touch_adr, ts); PUT(touch_type, ttype); PUT(touch_size, tsize);
-  {
-    // every sensor in MuJoCo's order (stage_sensors): one scalar each, so nsensordata = nsensor
-    std::vector<int> stype = B.i("sensor_type"), sobj = B.i("sensor_objid"), sadr = B.i("sensor_adr");
-    nsensor = std::max(nsensor, 0);
-    if (nsensor > MAXSENS) return fail(AW_EUNSUPPORTED, "more sensors than MAXSENS");
-    if ((int)stype.size() != nsensor || (int)sobj.size() != nsensor || (int)sadr.size() != nsensor)
-      return fail(AW_EBLOB, "sensor arrays do not match nsensor");
-    for (int k = 0; k < nsensor; k++) {
-      const int lim = stype[k] == SENS_TOUCH ? nsite : stype[k] == SENS_JOINTPOS ? njnt
-                      : stype[k] == SENS_ACTUATORFRC ? nu : -1;
-      if (lim < 0) return fail(AW_EUNSUPPORTED, "sensor type (touch, jointpos and actuatorfrc are supported)");
-      if (sobj[k] < 0 || sobj[k] >= lim || sadr[k] < 0 || sadr[k] >= nsensor) return fail(AW_EBLOB, "sensor object / address out of range");
-    }
-    if (nsensor > 0 && !(B.has("site_type") && B.has("site_size"))) return fail(AW_EBLOB, "model table lacks the site shapes");
-    sens.n = nsensor;
-    sens.out = nullptr;
-    if (!put_arr(sens.type, stype) || !put_arr(sens.obj, sobj) || !put_arr(sens.adr, sadr) || !put_arr(sens.act_dof, trn) ||
-        !put_arr(sens.site_type, B.i("site_type")) || !put_arr(sens.site_size, tof(B.f("site_size"))))
-      return fail(AW_EUNSUPPORTED, "sensor tables exceed kernel capacity");
-  }
-  {
-    // depth renderer: every primitive (non-mesh) geom in model order
-    std::vector<int> rt, rb, rc;
-    std::vector<double> rp, rq, rs, rr;
-    for (int g = 0; g < ngeom_all; g++) {
-      if (gtype[g] == 7) continue;
-      rt.push_back(gtype[g]); rb.push_back(gbody[g]); rc.push_back(gmap[g]);
-      for (int k = 0; k < 3; k++) { rp.push_back(gpos[3 * g + k]); rs.push_back(gsize[3 * g + k]); }
-      for (int k = 0; k < 4; k++) rq.push_back(gquat[4 * g + k]);
-      rr.push_back(grb[g]);
-    }
-    m.nrgeom = (int)rt.size();
-    // colour renderer: the visible sites (group 0-2, alpha > 0) follow the geoms, then every
-    // entry's colour record.  A model table without the appearance arrays renders depth only.
-    std::vector<int> rsite(rt.size(), -1);
-    std::vector<float> rcol;
-    m.appearance = B.has("geom_rgba") && B.has("geom_group") && B.has("geom_matid") && B.has("site_rgba") &&
-                   B.has("site_group") && B.has("site_matid") && B.has("site_type") && B.has("site_size") &&
-                   B.has("mat_rgba") && B.has("light_pos");
-    if (m.appearance) {
-      std::vector<double> grgba = B.f("geom_rgba"), srgba = B.f("site_rgba"), mrgba = B.f("mat_rgba"),
-                          mspec = B.f("mat_specular"), mshin = B.f("mat_shininess"), memi = B.f("mat_emission"),
-                          spos = B.f("site_pos"), squat = B.f("site_quat"), ssize = B.f("site_size");
-      std::vector<int> ggroup = B.i("geom_group"), gmat = B.i("geom_matid"), sgroup = B.i("site_group"),
-                       smat = B.i("site_matid"), stype = B.i("site_type"), sbody = B.i("site_bodyid");
-      const int nmat = (int)mspec.size();
-      // rgb: an explicit rgba, else the material's (MuJoCo: a geom rgba left at its default
-      // 0.5 0.5 0.5 1 yields to the material); alpha as written
-      auto record = [&](int src_mat, const double* src_rgba, double alpha) {
-        const bool dflt = src_rgba[0] == 0.5 && src_rgba[1] == 0.5 && src_rgba[2] == 0.5 && src_rgba[3] == 1.0;
-        const double* c = (src_mat >= 0 && dflt) ? &mrgba[4 * src_mat] : src_rgba;
-        for (int k = 0; k < 3; k++) rcol.push_back((float)c[k]);
-        rcol.push_back((float)alpha);
-        rcol.push_back((float)(src_mat >= 0 ? mspec[src_mat] : 0.5));
-        rcol.push_back((float)(128.0 * (src_mat >= 0 ? mshin[src_mat] : 0.5)));
-        rcol.push_back((float)(src_mat >= 0 ? memi[src_mat] : 0.0));
-        rcol.push_back(0.f);
-      };
-      for (int g = 0; g < ngeom_all; g++) {
-        if (gtype[g] == 7) continue;
-        if (gmat[g] >= nmat) return fail(AW_EBLOB, "geom material id out of range");
-        // stand-in rule: a primitive in a group hidden by default (>= 3) is drawn in place of its
-        // body's mesh (absent), with the first mesh geom's colour and material; geoms are opaque
-        int src = g;
-        if (ggroup[g] >= 3)
-          for (int q = 0; q < ngeom_all; q++)
-            if (gtype[q] == 7 && gbody[q] == gbody[g]) { src = q; break; }
-        if (gmat[src] >= nmat) return fail(AW_EBLOB, "geom material id out of range");
-        record(gmat[src], &grgba[4 * src], 1.0);
-      }
-      for (int i = 0; i < nsite; i++) {
-        if (sgroup[i] > 2 || !(srgba[4 * i + 3] > 0)) continue;
-        if (smat[i] >= nmat) return fail(AW_EBLOB, "site material id out of range");
-        rt.push_back(stype[i]); rb.push_back(sbody[i]); rc.push_back(-1); rsite.push_back(i);
-        for (int k = 0; k < 3; k++) { rp.push_back(spos[3 * i + k]); rs.push_back(ssize[3 * i + k]); }
-        for (int k = 0; k < 4; k++) rq.push_back(squat[4 * i + k]);
-        const double* z = &ssize[3 * i];
-        rr.push_back(stype[i] == GEOM_SPHERE ? z[0] : stype[i] == GEOM_CAPSULE ? z[0] + z[1]
-                     : stype[i] == GEOM_CYLINDER ? std::sqrt(z[0] * z[0] + z[1] * z[1])
-                     : stype[i] == GEOM_BOX ? std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]) : 0.0);
-        record(smat[i], &srgba[4 * i], srgba[4 * i + 3]);
-      }
-      m.nrsite = (int)rt.size() - m.nrgeom;
-      if ((int)rt.size() > MAXRG) return fail(AW_EBLOB, "more render entries (primitive geoms + visible sites) than MAXRG");
-      // lights: positional lights with a cutoff below 180 degrees carry cos(cutoff), the others -2
-      std::vector<double> lpos = B.f("light_pos"), ldir = B.f("light_dir"), lamb = B.f("light_ambient"),
-                          ldif = B.f("light_diffuse"), lspe = B.f("light_specular"), latt = B.f("light_attenuation"),
-                          lcut = B.f("light_cutoff"), lexp = B.f("light_exponent");
-      std::vector<int> ldirl = B.i("light_directional");
-      m.nlight = (int)lcut.size();
-      if (m.nlight > MAXLIGHT) return fail(AW_EBLOB, "more lights than MAXLIGHT");
-      std::vector<float> lrec;
-      for (int l = 0; l < m.nlight; l++) {
-        for (const std::vector<double>* v : {&lpos, &ldir, &lamb, &ldif, &lspe, &latt})
-          for (int k = 0; k < 3; k++) lrec.push_back((float)(*v)[3 * l + k]);
-        lrec.push_back(!ldirl[l] && lcut[l] < 180.0 ? (float)std::cos(lcut[l] * 3.14159265358979323846 / 180.0) : -2.f);
-        lrec.push_back((float)lexp[l]);
-        lrec.push_back(ldirl[l] ? 1.f : 0.f);
-        lrec.resize((size_t)(l + 1) * LIGHT_W, 0.f);
-      }
-      PUT(light, lrec);
-      // tint rows of the task block
-      std::vector<int> tint = B.i("task_tint");
-      std::vector<double> tscale = B.f("task_tint_scale");
-      m.ntint = (int)tscale.size();
-      if (m.ntint > MAXTINT || (int)tint.size() != 3 * m.ntint) return fail(AW_EBLOB, "bad tint rows");
-      std::vector<int> te, tc, tsl;
-      for (int t = 0; t < m.ntint; t++) {
-        if (tint[3 * t] < 0 || tint[3 * t] >= (int)rt.size() || tint[3 * t + 1] < 0 || tint[3 * t + 1] > 2 ||
-            tint[3 * t + 2] < 0 || tint[3 * t + 2] >= m.nparam)
-          return fail(AW_EBLOB, "tint row out of range");
-        te.push_back(tint[3 * t]); tc.push_back(tint[3 * t + 1]); tsl.push_back(tint[3 * t + 2]);
-      }
-      PUT(tint_entry, te); PUT(tint_chan, tc); PUT(tint_slot, tsl); PUT(tint_scale, tof(tscale));
-    }
-    PUT(rg_type, rt); PUT(rg_body, rb); PUT(rg_cgeom, rc); PUT(rg_pos, rp); PUT(rg_quat, rq);
-    PUT(rg_size, rs); PUT(rg_rbound, rr); PUT(rg_site, rsite); PUT(rg_col, rcol);
-  }
-  {
-    // per-object "some parameter overrides this" flags (kinematics applies those overrides inline)
-    std::vector<int> bo(nbody, 0), so(std::max(nsite, 1), 0), go(std::max(m.ngeom, 1), 0);
-    for (int p = 0; p < m.nparam; p++) {
-      if (pf[p] == 0 || pf[p] == 1 || pf[p] == 3) bo[po[p]] = 1;
-      else if (pf[p] == 2) so[po[p]] = 1;
-      else if (pf[p] == 4 || pf[p] == 5) go[po[p]] = 1;
-    }
-    PUT(body_ovr, bo); PUT(site_ovr, so); PUT(geom_ovr, go);
-  }
-  PUT(task_idx, tidx); PUT(param_field, pf); PUT(param_obj, po); PUT(param_comp, pc);
-  PUT(act_mid, tof(B.f("task_act_mid"))); PUT(act_rng, tof(B.f("task_act_rng")));
-  PUT(param_default, tof(B.f("task_param_default")));
-  PUT(param_draw, B.i("task_param_draw"));
-  std::vector<double> dlo = B.f("task_draw_lo"), dhi = B.f("task_draw_hi");
-  m.ndraw = (int)dlo.size();
-  if (m.ndraw > 8) return fail(AW_EUNSUPPORTED, "too many reset draws");
-  PUT(draw_lo, tof(dlo)); PUT(draw_hi, tof(dhi));
-  return AW_OK;
-}
-
 #endif  // AW_TASK_TU
+
+// resident workgroups of a one-wave kernel on the device (occupancy x CUs): a persistent grid
+template <class K>
+static int resident_slots(K kernel, int device) {
+  int per_cu = 0, cus = 0;
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  return std::max(per_cu, 1) * std::max(cus, 1);
+}
+// launch(SENS, DATA) with the handle's switches as compile-time booleans: the step kernels'
+// instantiation that also evaluates the sensors (aw_set_sensors) / writes the mjData views (aw_set_data)
+template <class F>
+static void with_sens_data(const aw_handle* h, F launch) {
+  using T = std::true_type;
+  using N = std::false_type;
+  switch ((h->sensors ? 1 : 0) | (h->data_groups ? 2 : 0)) {
+    case 3: launch(T{}, T{}); break;
+    case 2: launch(N{}, T{}); break;
+    case 1: launch(T{}, N{}); break;
+    default: launch(N{}, N{}); break;
+  }
+}
 
 // The wide tier's launcher table, defined in the -DAW_WIDE -DAW_TASK_TU=TASK translation unit
 // (k_step_wide<TASK>): `run` drains the queue that the fast launch before it filled.
@@ -1706,24 +1277,12 @@ template <int TASK> const WideOps* wide_ops();
 
 #ifdef AW_WIDE
 template <int TASK>
-static int wide_slots(int device) {
-  int per_cu = 0, cus = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step_wide<TASK, false, false>), 64, 0);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  return std::max(per_cu, 1) * std::max(cus, 1);
-}
-template <int TASK>
 static void launch_wide(aw_handle* h, const float* a, float* obs, float* rew, uint8_t* done, uint8_t* goal,
                         float* tobs, int autoreset, uint64_t seed, hipStream_t st) {
-#define AW_LAUNCH_WIDE(S, D)                                                                                          \
-  hipLaunchKernelGGL((k_step_wide<TASK, S, D>), dim3(h->wide_grid), dim3(64), 0, st, (const DModel*)h->dmhdr_wide, a, \
-                     obs, rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv)
-  if (h->data_groups) {   // aw_set_data: the instantiations that also write the mjData views
-    if (h->sensors) AW_LAUNCH_WIDE(true, true); else AW_LAUNCH_WIDE(false, true);
-  } else {
-    if (h->sensors) AW_LAUNCH_WIDE(true, false); else AW_LAUNCH_WIDE(false, false);
-  }
-#undef AW_LAUNCH_WIDE
+  with_sens_data(h, [&](auto S, auto D) {
+    hipLaunchKernelGGL((k_step_wide<TASK, decltype(S)::value, decltype(D)::value>), dim3(h->wide_grid), dim3(64), 0, st,
+                       (const DModel*)h->dmhdr_wide, a, obs, rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv);
+  });
 }
 template <int TASK>
 static void launch_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, hipStream_t st) {
@@ -1733,19 +1292,12 @@ static void launch_dump_wide(aw_handle* h, int env, const float* ctrl, float* ou
   hipLaunchKernelGGL((k_dump_wide<TASK>), dim3(1), dim3(64), 0, st, mw, h->st, env, ctrl, out);
 }
 template <int TASK> const WideOps* wide_ops() {
-  static const WideOps ops = {wide_slots<TASK>, launch_wide<TASK>, launch_dump_wide<TASK>};
+  static const WideOps ops = {[](int device) { return resident_slots(k_step_wide<TASK, false, false>, device); },
+                              launch_wide<TASK>, launch_dump_wide<TASK>};
   return &ops;
 }
 template const WideOps* wide_ops<AW_TASK_TU>();
 #else
-// resident k_step workgroups on the handle's device (occupancy x CUs): the persistent grid
-template <int TASK>
-static int step_slots(int device) {
-  int per_cu = 0, cus = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_step<TASK, false, false>), 64, 0);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  return std::max(per_cu, 1) * std::max(cus, 1);
-}
 // Claim order for the next k_step launch (longest processing time first): per XCD class c (k_step's
 // env range [n c / 8, n (c + 1) / 8)) the envs are bucketed by their last env-step's shader cycles
 // on a quarter-octave scale and written costliest bucket first into perm (positions of the same
@@ -1790,16 +1342,10 @@ static void launch_step(aw_handle* h, const float* a, float* obs, float* rew, ui
   if (grid < h->nenv && (grid & 7) == 0)   // the XCD-class claim path (k_step xmap)
     hipLaunchKernelGGL(k_order, dim3(8), dim3(1024), 0, st, reinterpret_cast<const unsigned*>(h->next_env + 10 + h->nenv),
                        h->next_env + 10 + 2 * h->nenv, h->nenv);
-  // aw_set_sensors / aw_set_data: the instantiation that also evaluates the sensors / writes the mjData views
-#define AW_LAUNCH_STEP(S, D)                                                                                          \
-  hipLaunchKernelGGL((k_step<TASK, S, D>), dim3(grid), dim3(64), 0, st, h->m, (const DModel*)h->dmhdr, h->st, h->nenv, a, \
-                     obs, rew, done, goal, tobs, autoreset, seed, h->next_env)
-  if (h->data_groups) {
-    if (h->sensors) AW_LAUNCH_STEP(true, true); else AW_LAUNCH_STEP(false, true);
-  } else {
-    if (h->sensors) AW_LAUNCH_STEP(true, false); else AW_LAUNCH_STEP(false, false);
-  }
-#undef AW_LAUNCH_STEP
+  with_sens_data(h, [&](auto S, auto D) {
+    hipLaunchKernelGGL((k_step<TASK, decltype(S)::value, decltype(D)::value>), dim3(grid), dim3(64), 0, st, h->m,
+                       (const DModel*)h->dmhdr, h->st, h->nenv, a, obs, rew, done, goal, tobs, autoreset, seed, h->next_env);
+  });
   wide_ops<TASK>()->run(h, a, obs, rew, done, goal, tobs, autoreset, seed, st);
 }
 template <int TASK>
@@ -1853,7 +1399,8 @@ struct TaskOps {
 template <int TASK> const TaskOps* task_ops();
 #if !defined(AW_API_TU) && !defined(AW_WIDE)
 template <int TASK> const TaskOps* task_ops() {
-  static const TaskOps ops = {step_slots<TASK>, launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
+  static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
+                              launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>};
   return &ops;
 }
@@ -1863,45 +1410,33 @@ template const TaskOps* task_ops<AW_TASK_TU>();
 #endif
 #ifndef AW_TASK_TU
 
-// kernels are instantiated per task (the dof tree of aw_trees.h is a template argument)
+// The launcher tables of a task kind (kernels are instantiated per task: the dof tree of aw_trees.h
+// is a template argument); nullptr: not a task, or (-DAW_ONLY_TASK diagnostic builds) not in this build
+static const TaskOps* task_ops_of(int kind) {
+  switch (kind) {
 #ifdef AW_ONLY_TASK
-#define DISPATCH_TASK(T, CALL)                                                     \
-  switch (T) {                                                                     \
-    case AW_ONLY_TASK: CALL(AW_ONLY_TASK); break;                                  \
-    default: return fail(AW_EUNSUPPORTED, "task not instantiated in this build");  \
-  }
+    case AW_ONLY_TASK: return task_ops<AW_ONLY_TASK>();
 #else
-#define DISPATCH_TASK(T, CALL)                                                     \
-  switch (T) {                                                                     \
-    case 0: CALL(0); break;                                                        \
-    case 1: CALL(1); break;                                                        \
-    case 2: CALL(2); break;                                                        \
-    case 3: CALL(3); break;                                                        \
-    default: return fail(AW_EUNSUPPORTED, "task kind not instantiated (0..3)");   \
-  }
+    case 0: return task_ops<0>();
+    case 1: return task_ops<1>();
+    case 2: return task_ops<2>();
+    case 3: return task_ops<3>();
 #endif
-
-// the model's dof tree must be the compiled one of its task (aw_trees.h, tools/gen_trees.py)
-template <int TASK>
-static bool tree_matches(const std::vector<int>& par) {
-  if ((int)par.size() != TreeDef<TASK>::NV) return false;
-  for (int j = 0; j < TreeDef<TASK>::NV; j++)
-    if (par[j] != TreeDef<TASK>::parent[j]) return false;
-  return true;
-}
-static int check_tree(const Blob& B, int task_kind) {
-  const std::vector<int> par = B.i("dof_parentid");
-  bool ok = false;
-  switch (task_kind) {
-    case 0: ok = tree_matches<0>(par); break;
-    case 1: ok = tree_matches<1>(par); break;
-    case 2: ok = tree_matches<2>(par); break;
-    case 3: ok = tree_matches<3>(par); break;
-    default: return fail(AW_EUNSUPPORTED, "unknown task kind");
+    default: return nullptr;
   }
-  if (!ok) return fail(AW_EUNSUPPORTED, "model dof tree differs from the compiled tree of its task "
-                                        "(mj_envs_amd/csrc/aw_trees.h: run tools/gen_trees.py and rebuild)");
-  return AW_OK;
+}
+static const WideOps* wide_ops_of(int kind) {
+  switch (kind) {
+#ifdef AW_ONLY_TASK
+    case AW_ONLY_TASK: return wide_ops<AW_ONLY_TASK>();
+#else
+    case 0: return wide_ops<0>();
+    case 1: return wide_ops<1>();
+    case 2: return wide_ops<2>();
+    case 3: return wide_ops<3>();
+#endif
+    default: return nullptr;
+  }
 }
 
 // the fast tier's dense-row capacity of the handle's task: per task in the split build (each task's
@@ -1916,15 +1451,8 @@ static int fast_maxdense_handle(const aw_handle* h) {
 }
 
 // persistent grid of the k_step instantiation the handle currently selects
-static int update_slots(aw_handle* h) {
-  if (h->grid_env >= 0) {
-    h->slots = h->grid_env > 0 ? h->grid_env : (1 << 30);
-    return AW_OK;
-  }
-#define CALL(TT) (h->slots = task_ops<TT>()->slots(h->device))
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
-  return AW_OK;
+static void update_slots(aw_handle* h) {
+  h->slots = h->grid_env > 0 ? h->grid_env : h->grid_env == 0 ? (1 << 30) : h->ops->slots(h->device);
 }
 
 extern "C" {
@@ -1972,10 +1500,16 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   std::unique_ptr<MData> md(new MData());   // value-initialised: zero
   SensTab sens = {};
   DataTab data = {};
-  if (int rc = build_model(B, h->m, *md, sens, data)) return rc;
+  std::string err;
+  if (int rc = build_model(B, h->m, *md, sens, data, err)) return fail(rc, err);
   h->NV = h->m.nv;
   h->nsensor = sens.n;
-  if (int rc = check_tree(B, h->m.task_kind)) return rc;
+  if (int rc = check_tree(B, h->m.task_kind, err)) return fail(rc, err);
+  std::vector<float> def;   // default params of every env
+  if (int rc = param_defaults(B, h->m.nparam, def, err)) return fail(rc, err);
+  h->ops = task_ops_of(h->m.task_kind);
+  h->wide = wide_ops_of(h->m.task_kind);
+  if (!h->ops || !h->wide) return fail(AW_EUNSUPPORTED, "task not instantiated in this build");
   HIPCHK(hipSetDevice(device));
   HIPCHK(hipMalloc(&h->dmodel, sizeof(MData)));
   HIPCHK(hipMemcpy(h->dmodel, md.get(), sizeof(MData), hipMemcpyHostToDevice));
@@ -1988,9 +1522,7 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   HIPCHK(hipMalloc((void**)&h->next_env, nq * sizeof(int)));
   HIPCHK(hipMemset(h->next_env, 0, nq * sizeof(int)));
   // wide tier: its persistent grid and one spill block per wide workgroup
-#define CALL(TT) (h->wide_grid = std::min(n_envs, wide_ops<TT>()->slots(device)))
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->wide_grid = std::min(n_envs, h->wide->slots(device));
   HIPCHK(hipMalloc((void**)&h->jspill_wide, (size_t)h->wide_grid * JSPILL_WIDE * sizeof(float)));
   HIPCHK(hipMalloc((void**)&h->mfac_wide, (size_t)h->wide_grid * MFAC * sizeof(float)));
   HIPCHK(hipMalloc(&h->dmhdr_wide, sizeof(DModel) + sizeof(DState)));
@@ -1998,12 +1530,10 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   HIPCHK(hipMalloc(&h->dstate, bytes));
   HIPCHK(hipMemset(h->dstate, 0, bytes));
   layout_state(h.get(), (char*)h->dstate);
-  // default params for every env
   size_t N = (size_t)n_envs, np = std::max(h->m.nparam, 1);
   std::vector<float> prm(N * np, 0.f);
-  std::vector<double> def = B.f("task_param_default");
   for (size_t e = 0; e < N; e++)
-    for (int k = 0; k < h->m.nparam; k++) prm[e * np + k] = (float)def[k];
+    for (int k = 0; k < h->m.nparam; k++) prm[e * np + k] = def[k];
   HIPCHK(hipMemcpy(h->st.params, prm.data(), prm.size() * 4, hipMemcpyHostToDevice));
   if (int rc2 = upload_header(h.get())) return rc2;
   // the sensor block last, so that every block above sits where it sat without it
@@ -2014,7 +1544,7 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   HIPCHK(hipMemcpy(h->ddata, &data, sizeof(DataTab), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(((MData*)h->dmodel)->data, &h->ddata, sizeof(void*), hipMemcpyHostToDevice));
   if (const char* e = getenv("AW_STEP_GRID")) h->grid_env = std::max(atoi(e), 0);
-  if (int rc3 = update_slots(h.get())) return rc3;
+  update_slots(h.get());
   *out = h.release();
   return AW_OK;
 }
@@ -2154,9 +1684,7 @@ int aw_set_fault(aw_handle* h, int kind, int arg) {
 int aw_reset(aw_handle* h, const uint8_t* mask, const float* params, uint64_t seed, float* obs, void* stream) {
   if (!h) return fail(AW_EINVAL, "aw_reset: null");
   HIPCHK(hipSetDevice(h->device));
-#define CALL(TT) task_ops<TT>()->reset(h, mask, params, seed, obs, (hipStream_t)stream)
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->ops->reset(h, mask, params, seed, obs, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -2165,9 +1693,7 @@ int aw_step(aw_handle* h, const float* actions, float* obs, float* reward, uint8
             float* terminal_obs, int autoreset, uint64_t seed, void* stream) {
   if (!h || !actions || !obs || !reward || !done || !goal) return fail(AW_EINVAL, "aw_step: null buffer");
   HIPCHK(hipSetDevice(h->device));
-#define CALL(TT) task_ops<TT>()->step(h, actions, obs, reward, done, goal, terminal_obs, autoreset, seed, (hipStream_t)stream)
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->ops->step(h, actions, obs, reward, done, goal, terminal_obs, autoreset, seed, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -2199,9 +1725,7 @@ int aw_set_state(aw_handle* h, const float* qpos, const float* qvel, const float
                  float* obs, void* stream) {
   if (!h) return fail(AW_EINVAL, "aw_set_state: null");
   HIPCHK(hipSetDevice(h->device));
-#define CALL(TT) task_ops<TT>()->set(h, qpos, qvel, warm, params, obs, (hipStream_t)stream)
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->ops->set(h, qpos, qvel, warm, params, obs, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -2306,9 +1830,7 @@ int aw_task_eval(aw_handle* h, int n, const float* qpos, const float* qvel, cons
 int aw_forward_dump(aw_handle* h, int env, const float* ctrl, float* out, void* stream) {
   if (!h || !out || env < 0 || env >= h->nenv) return fail(AW_EINVAL, "aw_forward_dump: bad arguments");
   HIPCHK(hipSetDevice(h->device));
-#define CALL(TT) task_ops<TT>()->dump(h, env, ctrl, out, (hipStream_t)stream)
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->ops->dump(h, env, ctrl, out, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -2316,9 +1838,7 @@ int aw_forward_dump(aw_handle* h, int env, const float* ctrl, float* out, void* 
 int aw_forward_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, void* stream) {
   if (!h || !out || env < 0 || env >= h->nenv) return fail(AW_EINVAL, "aw_forward_dump_wide: bad arguments");
   HIPCHK(hipSetDevice(h->device));
-#define CALL(TT) wide_ops<TT>()->dump(h, env, ctrl, out, (hipStream_t)stream)
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->wide->dump(h, env, ctrl, out, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -2329,9 +1849,7 @@ int aw_render_depth(aw_handle* h, const float* cam, int width, int height, float
   HIPCHK(hipSetDevice(h->device));
   CamRec c;
   memcpy(c.c, cam, sizeof(c.c));   // host array: the camera record travels as a kernel argument
-#define CALL(TT) task_ops<TT>()->depth(h, c, width, height, out, (hipStream_t)stream)
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->ops->depth(h, c, width, height, out, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -2347,9 +1865,7 @@ int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, 
   memcpy(c.c, cam, sizeof(c.c));
   LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
   if (look) memcpy(l.c, look, sizeof(l.c));
-#define CALL(TT) task_ops<TT>()->rgb(h, c, l, width, height, ss, rgb, depth, (hipStream_t)stream)
-  DISPATCH_TASK(h->m.task_kind, CALL)
-#undef CALL
+  h->ops->rgb(h, c, l, width, height, ss, rgb, depth, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }

@@ -1083,7 +1083,7 @@ AW_DEV bool mpr_may_touch(const DModel& m, const Env& s, int pair) {
 }
 
 // ---------------------------------------------------------------------------------------
-// narrowphase of one pair of collider class C (host: adroit_wave.hip build_model pcls):
+// narrowphase of one pair of collider class C (host: aw_model_host.h pair_classes pcls):
 // 0 plane-*, 1 sphere/capsule pairs, 2 sphere/capsule-box, 3 box-box, 4 anything with a
 // cylinder (MPR).  The class is a template parameter so each class loop carries only its own
 // colliders (no divergent merge of every collider's code and registers).
