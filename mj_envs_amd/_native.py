@@ -27,7 +27,7 @@ ST_OVERFLOW = ST_CON_OVERFLOW | ST_EFC_OVERFLOW   # constraints dropped at MuJoC
 
 
 def dump_layout(maxcon=MAXCON, maxefc=MAXEFC):
-    """float offsets inside the aw_forward_dump output (adroit_wave.hip k_dump, DUMP_*)"""
+    """float offsets inside the aw_forward_dump output (aw_kernels.hip k_dump, DUMP_*)"""
     c, e = 1768, 1768 + 14 * maxcon
     return dict(xpos=(0, 96), xquat=(96, 128), site_xpos=(224, 96), qacc_smooth=(320, 36),
                 qfrc_smooth=(356, 36), qacc=(392, 36), qfrc_constraint=(428, 36), qM=(464, 1296),

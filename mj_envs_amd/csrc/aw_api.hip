@@ -1,0 +1,630 @@
+// aw_api.hip -- the C-ABI of the MI355X batched Adroit simulator (include/adroit_wave.h): the
+// handle, the host side of every aw_* entry point, and the task-independent kernels.  It
+// instantiates no per-task kernel: those come from the task units (aw_kernels.hip), reached through
+// the launcher tables task_ops<TASK> / wide_ops<TASK> (aw_handle.h) across the link.
+// The model table -> device tables builder is host-only code of its own: aw_model_host.h.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/adroit_wave.h"
+#include "../../include/aw_blob.h"
+#include "aw_collide.h"
+#include "aw_common.h"
+#include "aw_handle.h"
+#include "aw_model_host.h"
+#include "aw_policy.h"
+#include "aw_task.h"
+
+using namespace aw;
+
+// ---------------------------------------------------------------------------------------
+// the task-independent kernels
+__global__ void __launch_bounds__(64) k_task_eval(DModel m, int n, const float* qpos, const float* qvel,
+                                                  const float* xpos, const float* xquat, const float* sxpos,
+                                                  const float* touch, float* obs, float* reward, uint8_t* done,
+                                                  uint8_t* goal) {
+  __shared__ Env s;
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= n) return;
+  if (lane < m.nq) { s.qpos[lane] = qpos[(size_t)i * m.nq + lane]; s.qlo[lane] = 0.f; }
+  if (lane < m.nv) s.qvel[lane] = qvel[(size_t)i * m.nv + lane];
+  for (int k = lane; k < m.nbody * 3; k += 64) (&s.xpos[0][0])[k] = xpos[(size_t)i * m.nbody * 3 + k];
+  for (int k = lane; k < m.nbody * 4; k += 64) (&s.xquat[0][0])[k] = xquat[(size_t)i * m.nbody * 4 + k];
+  for (int k = lane; k < m.nsite * 3; k += 64) (&s.sxpos[0][0])[k] = sxpos[(size_t)i * m.nsite * 3 + k];
+  if (lane == 0) s.touch[0] = touch ? touch[i] : 0.f;
+  wsync();
+  write_obs(m, s, lane, obs + (size_t)i * m.obs_dim);
+  if (lane == 0) {
+    float r;
+    int dn, gl;
+    task_reward(m, s, &r, &dn, &gl);
+    reward[i] = r; done[i] = (uint8_t)dn; goal[i] = (uint8_t)gl;
+  }
+}
+
+// Test hook (aw_collide_test): the narrowphase of one primitive pair per workgroup, given world
+// poses -- exact-geometry collider tests against the oracle's colliders.
+// Lanes 0..15 call it with the same pair (gl = lane): capsule-box runs on the 16-lane row and MPR
+// on lanes 0 and 1 as in the narrowphase, every other collider on lane 0.
+AW_DEV void collide_gv(const DModel& m, const GV& a, const GV& b, float margin, Emit& e, int gl) {
+  const int lo = a.type, hi = b.type;   // a.type <= b.type
+  if (hi == GEOM_BOX && lo == GEOM_CAPSULE) {
+    c_capsule_box(a, b, margin, e, gl);
+    return;
+  }
+  if (lo != GEOM_PLANE && (lo == GEOM_CYLINDER || hi == GEOM_CYLINDER)) {   // MPR on lanes 0 and 1
+    if (gl > 1) return;
+    const GV& g = gl ? b : a;
+    mpr::GVdT<double> own;
+    for (int k = 0; k < 3; k++) { own.pos[k] = g.pos[k]; own.size[k] = g.size[k]; }
+    for (int k = 0; k < 9; k++) own.mat[k] = g.mat[k];
+    own.type = g.type;
+    c_convex64(m, own, gl, (double)margin, e);
+    return;
+  }
+  if (gl != 0) return;
+  if (lo == GEOM_PLANE) {
+    if (hi == GEOM_SPHERE) c_plane_sphere(a.pos, a.mat, b.pos, b.size[0], margin, e);
+    else if (hi == GEOM_CAPSULE) c_plane_capsule(a, b, margin, e);
+    else if (hi == GEOM_CYLINDER) c_plane_cylinder(a, b, margin, e);
+    else if (hi == GEOM_BOX) c_plane_box(a, b, margin, e);
+  } else if (hi == GEOM_BOX && lo == GEOM_BOX) {
+    c_box_box(a, b, margin, e);
+  } else if (hi == GEOM_BOX) {
+    c_sphere_box_pt(a.pos, a.size[0], b, margin, e);
+  } else if (lo == GEOM_SPHERE && hi == GEOM_SPHERE) {
+    c_sphere_sphere(a.pos, a.size[0], b.pos, b.size[0], margin, e);
+  } else if (lo == GEOM_SPHERE) {
+    c_sphere_capsule(a, b, margin, e);
+  } else {
+    c_capsule_capsule(a, b, margin, e);
+  }
+}
+
+__global__ void __launch_bounds__(64) k_collide_test(DModel m, int n, const int* types, const float* pos,
+                                                     const float* mat, const float* size, const float* margin,
+                                                     float* out, int* count, double* out64) {
+  __shared__ Env s;
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= n) return;
+  if (lane == 0) { s.ncon = 0; s.status = 0u; }
+  wsync();
+  if (lane < 16) {
+    GV g[2];
+    for (int q = 0; q < 2; q++) {
+      g[q].type = types[2 * i + q];
+      for (int k = 0; k < 3; k++) { g[q].pos[k] = pos[6 * i + 3 * q + k]; g[q].size[k] = size[6 * i + 3 * q + k]; }
+      for (int k = 0; k < 9; k++) g[q].mat[k] = mat[18 * i + 9 * q + k];
+    }
+    const int f = g[0].type <= g[1].type ? 0 : 1;
+    Emit e{&s, 0, 0, out64 ? out64 + (size_t)i * MAXPAIRCON * 7 : nullptr};
+    collide_gv(m, g[f], g[1 - f], margin[i], e, lane);
+  }
+  wsync();
+  const int nc = s.ncon < MAXPAIRCON ? s.ncon : MAXPAIRCON;
+  if (lane == 0) count[i] = nc;
+  if (lane < nc) {
+    float* o = out + ((size_t)i * MAXPAIRCON + s.con_key[lane]) * 7;   // emission order
+    o[0] = s.con_dist[lane];
+    for (int k = 0; k < 3; k++) { o[1 + k] = s.con_pos[lane][k]; o[4 + k] = s.con_nrm[lane][k]; }
+  }
+}
+
+__global__ void k_random_actions(int n, int nu, uint64_t seed, uint64_t step, uint64_t env_offset, float* out) {
+  int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env >= n) return;
+  const uint32_t genv = (uint32_t)(env_offset + (uint64_t)env);   // global env id (shard offset)
+  for (int blk = 0; blk * 4 < nu; blk++) {
+    uint32_t c[4] = {genv, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)blk};
+    philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    for (int k = 0; k < 4 && blk * 4 + k < nu; k++) out[(size_t)env * nu + blk * 4 + k] = 2.f * u01(c[k]) - 1.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// host side
+namespace {
+thread_local std::string g_err;
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(AW_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+}  // namespace
+
+static int upload_header(aw_handle* h) {
+  HIPCHK(hipMemcpy(h->dmhdr, &h->m, sizeof(DModel), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((DModel*)h->dmhdr + 1, &h->st, sizeof(DState), hipMemcpyHostToDevice));
+  DModel mw = h->m;
+  mw.jspill = h->jspill_wide;
+  mw.mfac = h->mfac_wide;
+  HIPCHK(hipMemcpy(h->dmhdr_wide, &mw, sizeof(DModel), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((DModel*)h->dmhdr_wide + 1, &h->st, sizeof(DState), hipMemcpyHostToDevice));
+  return AW_OK;
+}
+
+// The launcher tables of a task kind (kernels are instantiated per task: the dof tree of aw_trees.h
+// is a template argument); nullptr: not a task, or (-DAW_ONLY_TASK: a library that holds one task,
+// tools/stage_profile.py) not in this build
+static const TaskOps* task_ops_of(int kind) {
+  switch (kind) {
+#ifdef AW_ONLY_TASK
+    case AW_ONLY_TASK: return task_ops<AW_ONLY_TASK>();
+#else
+    case 0: return task_ops<0>();
+    case 1: return task_ops<1>();
+    case 2: return task_ops<2>();
+    case 3: return task_ops<3>();
+#endif
+    default: return nullptr;
+  }
+}
+static const WideOps* wide_ops_of(int kind) {
+  switch (kind) {
+#ifdef AW_ONLY_TASK
+    case AW_ONLY_TASK: return wide_ops<AW_ONLY_TASK>();
+#else
+    case 0: return wide_ops<0>();
+    case 1: return wide_ops<1>();
+    case 2: return wide_ops<2>();
+    case 3: return wide_ops<3>();
+#endif
+    default: return nullptr;
+  }
+}
+
+// persistent grid of the k_step instantiation the handle currently selects
+static void update_slots(aw_handle* h) {
+  h->slots = h->grid_env > 0 ? h->grid_env : h->grid_env == 0 ? (1 << 30) : h->ops->slots(h->device);
+}
+
+// device-to-device copies of per-env arrays on one stream, in list order; a field whose caller-side
+// end is null is skipped (the getters and setters of the state, episode and status arrays)
+struct CopyField {
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+static int copy_fields(std::initializer_list<CopyField> fields, void* stream) {
+  for (const CopyField& f : fields)
+    if (f.dst && f.src) HIPCHK(hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return AW_OK;
+}
+
+extern "C" {
+
+const char* aw_last_error(void) { return g_err.c_str(); }
+
+static void free_handle(aw_handle* h) {
+  if (!h) return;
+  if (h->dmodel) (void)hipFree(h->dmodel);
+  if (h->dmhdr) (void)hipFree(h->dmhdr);
+  if (h->dstate) (void)hipFree(h->dstate);
+  if (h->m.jspill) (void)hipFree(h->m.jspill);
+  if (h->m.mfac) (void)hipFree(h->m.mfac);
+  if (h->next_env) (void)hipFree(h->next_env);
+  if (h->dmhdr_wide) (void)hipFree(h->dmhdr_wide);
+  if (h->jspill_wide) (void)hipFree(h->jspill_wide);
+  if (h->mfac_wide) (void)hipFree(h->mfac_wide);
+  if (h->dsens) (void)hipFree(h->dsens);
+  if (h->ddata) (void)hipFree(h->ddata);
+  if (h->sensordata) (void)hipFree(h->sensordata);
+  delete h;
+}
+
+// carve the per-env state arrays out of one allocation (each 256-byte aligned)
+static size_t layout_state(aw_handle* h, char* base) {
+  size_t N = (size_t)h->nenv, nq = h->m.nq, nv = h->m.nv, np = std::max(h->m.nparam, 1);
+  uintptr_t p = (uintptr_t)base;   // base == nullptr: dry run, only the size is used
+  auto take = [&](size_t b) { uintptr_t r = p; p += (b + 255) & ~size_t(255); return (char*)r; };
+  DState& st = h->st;
+  st.qpos = (float*)take(N * nq * 4); st.qvel = (float*)take(N * nv * 4); st.warm = (float*)take(N * nv * 4);
+  st.params = (float*)take(N * np * 4); st.ep_len = (int*)take(N * 4); st.ep_ret = (float*)take(N * 4);
+  st.ep_goal = (int*)take(N * 4); st.episode = (int*)take(N * 4); st.status = (unsigned*)take(N * 4);
+  st.last_ret = (float*)take(N * 4); st.last_goal = (int*)take(N * 4); st.last_len = (int*)take(N * 4);
+  st.status_acc = (unsigned*)take(N * 4); st.sum_ret = (float*)take(N * 4); st.n_success = (int*)take(N * 4);
+  return (size_t)(p - (uintptr_t)base);
+}
+
+int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle** out) {
+  if (!blob || !out || n_envs <= 0) return fail(AW_EINVAL, "aw_create: bad arguments");
+  *out = nullptr;
+  Blob B{blob, nbytes};
+  std::unique_ptr<aw_handle, void (*)(aw_handle*)> h(new aw_handle(), free_handle);
+  h->device = device;
+  h->nenv = n_envs;
+  std::unique_ptr<MData> md(new MData());   // value-initialised: zero
+  SensTab sens = {};
+  DataTab data = {};
+  std::string err;
+  if (int rc = build_model(B, h->m, *md, sens, data, err)) return fail(rc, err);
+  h->NV = h->m.nv;
+  h->nsensor = sens.n;
+  if (int rc = check_tree(B, h->m.task_kind, err)) return fail(rc, err);
+  std::vector<float> def;   // default params of every env
+  if (int rc = param_defaults(B, h->m.nparam, def, err)) return fail(rc, err);
+  h->ops = task_ops_of(h->m.task_kind);
+  h->wide = wide_ops_of(h->m.task_kind);
+  if (!h->ops || !h->wide) return fail(AW_EUNSUPPORTED, "task not instantiated in this build");
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipMalloc(&h->dmodel, sizeof(MData)));
+  HIPCHK(hipMemcpy(h->dmodel, md.get(), sizeof(MData), hipMemcpyHostToDevice));
+  h->m.d = (const MData*)h->dmodel;
+  // fast tier: one spill block per workgroup of k_reset / k_set_state (one per env)
+  HIPCHK(hipMalloc((void**)&h->m.jspill, (size_t)n_envs * JSPILL_FAST * sizeof(float)));
+  HIPCHK(hipMalloc((void**)&h->m.mfac, (size_t)n_envs * MFAC * sizeof(float)));
+  HIPCHK(hipMalloc(&h->dmhdr, sizeof(DModel) + sizeof(DState)));
+  const size_t nq = 10 + 3 * (size_t)n_envs;   // + per-env costs and the claim permutation (k_order)
+  HIPCHK(hipMalloc((void**)&h->next_env, nq * sizeof(int)));
+  HIPCHK(hipMemset(h->next_env, 0, nq * sizeof(int)));
+  // wide tier: its persistent grid and one spill block per wide workgroup
+  h->wide_grid = std::min(n_envs, h->wide->slots(device));
+  HIPCHK(hipMalloc((void**)&h->jspill_wide, (size_t)h->wide_grid * JSPILL_WIDE * sizeof(float)));
+  HIPCHK(hipMalloc((void**)&h->mfac_wide, (size_t)h->wide_grid * MFAC * sizeof(float)));
+  HIPCHK(hipMalloc(&h->dmhdr_wide, sizeof(DModel) + sizeof(DState)));
+  const size_t bytes = layout_state(h.get(), nullptr);   // dry run: sizes only
+  HIPCHK(hipMalloc(&h->dstate, bytes));
+  HIPCHK(hipMemset(h->dstate, 0, bytes));
+  layout_state(h.get(), (char*)h->dstate);
+  size_t N = (size_t)n_envs, np = std::max(h->m.nparam, 1);
+  std::vector<float> prm(N * np, 0.f);
+  for (size_t e = 0; e < N; e++)
+    for (int k = 0; k < h->m.nparam; k++) prm[e * np + k] = def[k];
+  HIPCHK(hipMemcpy(h->st.params, prm.data(), prm.size() * 4, hipMemcpyHostToDevice));
+  if (int rc2 = upload_header(h.get())) return rc2;
+  // the sensor block last, so that every block above sits where it sat without it
+  HIPCHK(hipMalloc(&h->dsens, sizeof(SensTab)));
+  HIPCHK(hipMemcpy(h->dsens, &sens, sizeof(SensTab), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(((MData*)h->dmodel)->sens, &h->dsens, sizeof(void*), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&h->ddata, sizeof(DataTab)));   // and the mjData output block after it (aw_set_data)
+  HIPCHK(hipMemcpy(h->ddata, &data, sizeof(DataTab), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(((MData*)h->dmodel)->data, &h->ddata, sizeof(void*), hipMemcpyHostToDevice));
+  if (const char* e = getenv("AW_STEP_GRID")) h->grid_env = std::max(atoi(e), 0);
+  update_slots(h.get());
+  *out = h.release();
+  return AW_OK;
+}
+
+int aw_destroy(aw_handle* h) {
+  if (!h) return AW_OK;
+  (void)hipSetDevice(h->device);
+  free_handle(h);
+  return AW_OK;
+}
+
+int aw_dims(const aw_handle* h, int* d) {
+  if (!h || !d) return fail(AW_EINVAL, "aw_dims: null");
+  const DModel& m = h->m;
+  int v[AW_NDIMS] = {m.nq, m.nv, m.nu, m.obs_dim, m.nparam, m.frame_skip, m.horizon, m.task_kind, h->nenv,
+                     m.nbody, m.nsite, m.ngeom, m.npairall, NCONMAX, NJMAX, WIDE_MAXDENSE, std::min(h->slots, h->nenv),
+                     FAST_MAXCON, 64 * FAST_NRL, fast_maxdense_of(m.task_kind), h->wide_grid};
+  memcpy(d, v, sizeof(v));
+  return AW_OK;
+}
+
+int aw_set_option(aw_handle* h, int disableflags, int iterations, int noslip_iterations) {
+  if (!h) return fail(AW_EINVAL, "aw_set_option: null");
+  if (disableflags >= 0 && (disableflags & ~0xFFFF))
+    return fail(AW_EUNSUPPORTED, "aw_set_option: only MuJoCo's disable bits 0..15 (the MPR collider always runs in fp64)");
+  if (disableflags >= 0) h->m.disableflags = disableflags;
+  if (iterations >= 0) h->m.iterations = iterations;
+  if (noslip_iterations >= 0) h->m.noslip_iterations = noslip_iterations;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // steps already queued on any stream read the old header
+  return upload_header(h);
+}
+
+int aw_set_tier(aw_handle* h, int mode) {
+  if (!h || mode < 0 || mode > 1) return fail(AW_EINVAL, "aw_set_tier: mode must be 0 (automatic) or 1 (wide only)");
+  h->m.force_wide = mode;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // queued launches read the old header
+  return upload_header(h);
+}
+
+int aw_set_sensors(aw_handle* h, int enable) {
+  if (!h || enable < 0 || enable > 1) return fail(AW_EINVAL, "aw_set_sensors: enable must be 0 or 1");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // queued launches read the old table
+  const size_t bytes = (size_t)h->nenv * std::max(h->nsensor, 1) * sizeof(float);
+  if (enable && !h->sensordata) HIPCHK(hipMalloc((void**)&h->sensordata, bytes));
+  if (enable && !h->sensors) HIPCHK(hipMemset(h->sensordata, 0, bytes));   // zero until an env's next forward
+  float* out = enable ? h->sensordata : nullptr;
+  HIPCHK(hipMemcpy(&((SensTab*)h->dsens)->out, &out, sizeof(out), hipMemcpyHostToDevice));
+  h->sensors = enable != 0;
+  return AW_OK;
+}
+
+static_assert(AW_DATA_MAX_CONTACTS == WIDE_MAXCON, "aw_set_data's contact cap is the wide tier's contact storage");
+static_assert(AW_CONTACT_DWORDS * 4 == 4 * sizeof(MRec), "a contact record is four 16-byte stores");
+int aw_set_data(aw_handle* h, int groups, int max_contacts, const aw_data_bufs* bufs) {
+  if (!h) return fail(AW_EINVAL, "aw_set_data: null");
+  if (groups & ~(AW_DATA_KIN | AW_DATA_DYN | AW_DATA_CONTACT)) return fail(AW_EINVAL, "aw_set_data: unknown group bits");
+  // the table's head (groups, capacity, buffers); geom_id behind it stays as aw_create wrote it
+  DataTab t;
+  memset(&t, 0, sizeof(t));
+  if (groups) {
+    if (!bufs) return fail(AW_EINVAL, "aw_set_data: no buffers");
+    if (max_contacts < 1 || max_contacts > AW_DATA_MAX_CONTACTS)
+      return fail(AW_EINVAL, "aw_set_data: max_contacts must be 1..128 (the wide tier's contact storage)");
+    if ((groups & AW_DATA_KIN) && !(bufs->xpos && bufs->xquat && bufs->site_xpos))
+      return fail(AW_EINVAL, "aw_set_data: AW_DATA_KIN needs xpos, xquat and site_xpos");
+    if ((groups & AW_DATA_DYN) && !(bufs->qacc && bufs->qfrc_constraint && bufs->counts))
+      return fail(AW_EINVAL, "aw_set_data: AW_DATA_DYN needs qacc, qfrc_constraint and counts");
+    if ((groups & AW_DATA_CONTACT) && !bufs->contact) return fail(AW_EINVAL, "aw_set_data: AW_DATA_CONTACT needs contact");
+    if ((groups & AW_DATA_CONTACT) && ((uintptr_t)bufs->contact & 15))
+      return fail(AW_EINVAL, "aw_set_data: contact must be 16-byte aligned");
+    t.groups = groups;
+    t.max_contacts = max_contacts;
+    // only the requested groups' pointers reach the device: the others are never dereferenced
+    if (groups & AW_DATA_KIN) { t.xpos = bufs->xpos; t.xquat = bufs->xquat; t.site_xpos = bufs->site_xpos; }
+    if (groups & AW_DATA_DYN) { t.qacc = bufs->qacc; t.qfrc_constraint = bufs->qfrc_constraint; t.counts = bufs->counts; }
+    if (groups & AW_DATA_CONTACT) t.contact = (MRec*)bufs->contact;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // queued launches read the old table
+  HIPCHK(hipMemcpy(h->ddata, &t, offsetof(DataTab, geom_id), hipMemcpyHostToDevice));
+  h->data_groups = groups;
+  return AW_OK;
+}
+
+int aw_sensor_count(const aw_handle* h) {
+  if (!h) return fail(AW_EINVAL, "aw_sensor_count: null");
+  return h->nsensor;
+}
+
+int aw_sensordata(aw_handle* h, float* out, void* stream) {
+  if (!h || !out) return fail(AW_EINVAL, "aw_sensordata: null");
+  if (!h->sensors) return fail(AW_EINVAL, "aw_sensordata: sensors are disabled (aw_set_sensors)");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(out, h->sensordata, (size_t)h->nenv * h->nsensor * sizeof(float), hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+  return AW_OK;
+}
+
+int aw_set_fault(aw_handle* h, int kind, int arg) {
+  if (!h || kind < 0 || kind > 2) return fail(AW_EINVAL, "aw_set_fault: kind must be 0 (none), 1 (margin) or 2 (stick row)");
+  if (kind == 2 && (arg < 0 || arg >= h->m.nfl)) return fail(AW_EINVAL, "aw_set_fault: no such frictionloss row");
+  if (kind == 1 && (arg < -1000 || arg > 1000)) return fail(AW_EINVAL, "aw_set_fault: margin shift beyond 1 mm");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // queued launches read the old table / header
+  MData* dm = (MData*)h->dmodel;
+  const int np = h->m.npairall;
+  if (h->fault_cls.empty()) {      // the table as built, saved once
+    h->fault_margin0.resize(np); h->fault_rb0.resize(np); h->fault_margin64_0.resize(np); h->fault_cls.resize(np);
+    HIPCHK(hipMemcpy(h->fault_margin0.data(), dm->cp_margin, np * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->fault_rb0.data(), dm->cp_rb, np * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->fault_margin64_0.data(), dm->cp_margin64, np * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->fault_cls.data(), dm->cp_class, np * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  std::vector<float> mg = h->fault_margin0, rb = h->fault_rb0;
+  std::vector<double> mg64 = h->fault_margin64_0;
+  if (kind == 1) {
+    // every sphere / capsule pair (collider class 1): activation, the fp64 decision, the rows'
+    // includemargin and the broadphase radius all see the shifted margin
+    const double dl = 1e-6 * arg;
+    for (int p = 0; p < np; p++)
+      if (h->fault_cls[p] == 1) {
+        mg64[p] += dl;
+        mg[p] = (float)mg64[p];
+        rb[p] = (float)((double)rb[p] + dl);
+      }
+  }
+  HIPCHK(hipMemcpy(dm->cp_margin, mg.data(), np * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dm->cp_rb, rb.data(), np * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dm->cp_margin64, mg64.data(), np * sizeof(double), hipMemcpyHostToDevice));
+  h->m.fault_flrow = kind == 2 ? arg : -1;
+  return upload_header(h);
+}
+
+int aw_reset(aw_handle* h, const uint8_t* mask, const float* params, uint64_t seed, float* obs, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_reset: null");
+  HIPCHK(hipSetDevice(h->device));
+  h->ops->reset(h, mask, params, seed, obs, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_step(aw_handle* h, const float* actions, float* obs, float* reward, uint8_t* done, uint8_t* goal,
+            float* terminal_obs, int autoreset, uint64_t seed, void* stream) {
+  if (!h || !actions || !obs || !reward || !done || !goal) return fail(AW_EINVAL, "aw_step: null buffer");
+  HIPCHK(hipSetDevice(h->device));
+  h->ops->step(h, actions, obs, reward, done, goal, terminal_obs, autoreset, seed, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_random_actions(aw_handle* h, uint64_t seed, uint64_t step, float* actions, void* stream) {
+  if (!h || !actions) return fail(AW_EINVAL, "aw_random_actions: null");
+  HIPCHK(hipSetDevice(h->device));
+  int bs = 256, nb = (h->nenv + bs - 1) / bs;
+  hipLaunchKernelGGL(k_random_actions, dim3(nb), dim3(bs), 0, (hipStream_t)stream, h->nenv, h->m.nu, seed, step,
+                     (uint64_t)h->m.env_offset, actions);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_get_state(aw_handle* h, float* qpos, float* qvel, float* warm, float* params, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_get_state: null");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t N = h->nenv;
+  const DState& s = h->st;
+  return copy_fields({{qpos, s.qpos, N * h->m.nq * 4}, {qvel, s.qvel, N * h->m.nv * 4}, {warm, s.warm, N * h->m.nv * 4},
+                      {h->m.nparam ? params : nullptr, s.params, N * h->m.nparam * 4}}, stream);
+}
+
+int aw_set_state(aw_handle* h, const float* qpos, const float* qvel, const float* warm, const float* params,
+                 float* obs, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_set_state: null");
+  HIPCHK(hipSetDevice(h->device));
+  h->ops->set(h, qpos, qvel, warm, params, obs, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_status(aw_handle* h, uint32_t* last, uint32_t* sticky, void* stream) {
+  if (!h || (!last && !sticky)) return fail(AW_EINVAL, "aw_status: null");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t b = (size_t)h->nenv * 4;
+  return copy_fields({{last, h->st.status, b}, {sticky, h->st.status_acc, b}}, stream);
+}
+
+int aw_clear_status(aw_handle* h, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_clear_status: null");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemsetAsync(h->st.status_acc, 0, (size_t)h->nenv * 4, (hipStream_t)stream));
+  return AW_OK;
+}
+
+int aw_set_env_offset(aw_handle* h, uint64_t env_offset) {
+  if (!h) return fail(AW_EINVAL, "aw_set_env_offset: null");
+  h->m.env_offset = env_offset;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // steps already queued read the old header
+  return upload_header(h);
+}
+
+int aw_get_episode(aw_handle* h, int32_t* ep_len, float* ep_ret, int32_t* ep_goal, int32_t* episodes,
+                   void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_get_episode: null");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t b = (size_t)h->nenv * 4;
+  const DState& s = h->st;
+  return copy_fields({{ep_len, s.ep_len, b}, {ep_ret, s.ep_ret, b}, {ep_goal, s.ep_goal, b}, {episodes, s.episode, b}},
+                     stream);
+}
+
+int aw_set_episode(aw_handle* h, const int32_t* ep_len, const float* ep_ret, const int32_t* ep_goal,
+                   const int32_t* episodes, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_set_episode: null");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t b = (size_t)h->nenv * 4;
+  const DState& s = h->st;
+  return copy_fields({{s.ep_len, ep_len, b}, {s.ep_ret, ep_ret, b}, {s.ep_goal, ep_goal, b}, {s.episode, episodes, b}},
+                     stream);
+}
+
+int aw_episode_totals(aw_handle* h, int32_t* episodes, float* sum_return, int32_t* successes, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_episode_totals: null");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t b = (size_t)h->nenv * 4;
+  const DState& s = h->st;
+  return copy_fields({{episodes, s.episode, b}, {sum_return, s.sum_ret, b}, {successes, s.n_success, b}}, stream);
+}
+
+int aw_set_episode_totals(aw_handle* h, const int32_t* episodes, const float* sum_return, const int32_t* successes,
+                          void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_set_episode_totals: null");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t b = (size_t)h->nenv * 4;
+  const DState& s = h->st;
+  return copy_fields({{s.episode, episodes, b}, {s.sum_ret, sum_return, b}, {s.n_success, successes, b}}, stream);
+}
+
+int aw_episode_stats(aw_handle* h, float* last_return, int32_t* last_goal, int32_t* last_len, int32_t* episodes,
+                     void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_episode_stats: null");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t b = (size_t)h->nenv * 4;
+  const DState& s = h->st;
+  return copy_fields({{last_return, s.last_ret, b}, {last_goal, s.last_goal, b}, {last_len, s.last_len, b},
+                      {episodes, s.episode, b}}, stream);
+}
+
+int aw_task_eval(aw_handle* h, int n, const float* qpos, const float* qvel, const float* xpos, const float* xquat,
+                 const float* sxpos, const float* touch, float* obs, float* reward, uint8_t* done, uint8_t* goal,
+                 void* stream) {
+  if (!h || n <= 0) return fail(AW_EINVAL, "aw_task_eval: bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_task_eval, dim3(n), dim3(64), 0, (hipStream_t)stream, h->m, n, qpos, qvel, xpos, xquat,
+                     sxpos, touch, obs, reward, done, goal);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_forward_dump(aw_handle* h, int env, const float* ctrl, float* out, void* stream) {
+  if (!h || !out || env < 0 || env >= h->nenv) return fail(AW_EINVAL, "aw_forward_dump: bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  h->ops->dump(h, env, ctrl, out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_forward_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, void* stream) {
+  if (!h || !out || env < 0 || env >= h->nenv) return fail(AW_EINVAL, "aw_forward_dump_wide: bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  h->wide->dump(h, env, ctrl, out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_render_depth(aw_handle* h, const float* cam, int width, int height, float* out, void* stream) {
+  if (!h || !cam || !out || width <= 0 || height <= 0 || width > 4096 || height > 4096)
+    return fail(AW_EINVAL, "aw_render_depth: bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  CamRec c;
+  memcpy(c.c, cam, sizeof(c.c));   // host array: the camera record travels as a kernel argument
+  h->ops->depth(h, c, width, height, out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, int height, int ss, uint8_t* rgb,
+                  float* depth, void* stream) {
+  if (!h || !cam || !rgb || width <= 0 || height <= 0 || width > 1024 || height > 1024 || (ss != 1 && ss != 2) ||
+      (depth && ss != 1))
+    return fail(AW_EINVAL, "aw_render_rgb: bad arguments");
+  if (!h->m.appearance) return fail(AW_EUNSUPPORTED, "aw_render_rgb: the model table carries no appearance arrays");
+  HIPCHK(hipSetDevice(h->device));
+  CamRec c;
+  memcpy(c.c, cam, sizeof(c.c));
+  LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
+  if (look) memcpy(l.c, look, sizeof(l.c));
+  h->ops->rgb(h, c, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_policy_mlp(int n, int in_dim, int hidden, int out_dim, const float* params, const float* obs, float* act,
+                  int sample, uint64_t seed, uint64_t step, uint64_t env_offset, void* stream) {
+  if (n <= 0 || !params || !obs || !act || in_dim <= 0 || in_dim > MLP_IMAX || out_dim <= 0 || out_dim > MLP_OMAX)
+    return fail(AW_EINVAL, "aw_policy_mlp: bad arguments");
+  const int bs = 256, nb = (n + bs - 1) / bs;
+  hipStream_t st = (hipStream_t)stream;
+  switch (hidden) {
+    case 32: hipLaunchKernelGGL(k_mlp<32>, dim3(nb), dim3(bs), 0, st, n, in_dim, out_dim, params, obs, act, sample, seed, step, env_offset); break;
+    case 64: hipLaunchKernelGGL(k_mlp<64>, dim3(nb), dim3(bs), 0, st, n, in_dim, out_dim, params, obs, act, sample, seed, step, env_offset); break;
+    default: return fail(AW_EUNSUPPORTED, "aw_policy_mlp: hidden width must be 32 or 64 (two hidden layers)");
+  }
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_collide_test(aw_handle* h, int n, const int32_t* types, const float* pos, const float* mat, const float* size,
+                    const float* margin, float* out, int32_t* count, double* out64, void* stream) {
+  if (!h || n <= 0 || !types || !pos || !mat || !size || !margin || !out || !count)
+    return fail(AW_EINVAL, "aw_collide_test: bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_collide_test, dim3(n), dim3(64), 0, st, h->m, n, types, pos, mat, size, margin, out, count, out64);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_stage_profile(unsigned long long* out, int reset) {
+#ifdef AW_STAGE_PROF
+  HIPCHK(stage_prof_read(out, reset));
+  return AW_OK;
+#else
+  (void)out; (void)reset;
+  return fail(AW_EUNSUPPORTED, "library built without -DAW_STAGE_PROF");
+#endif
+}
+
+}  // extern "C"

@@ -60,15 +60,13 @@ constexpr int FAST_MAXDENSE_ALLOC = 192;
 // always-inline function taking one -- at different sizes, so their mangled names must differ too.
 #if defined(AW_FAST_MAXDENSE)
 #define AW_FAST_MD AW_FAST_MAXDENSE   // explicit override (tools/build_variant.py): a literal
-#elif (defined(AW_TASK_TU) && AW_TASK_TU == 3) || (defined(AW_ONLY_TASK) && AW_ONLY_TASK == 3)
+#elif defined(AW_TASK_TU) && AW_TASK_TU == 3
 #define AW_FAST_MD 192
 #else
-#define AW_FAST_MD 128   // the other tasks, the API unit, single-TU builds of all four tasks
+#define AW_FAST_MD 128   // the other tasks; the API unit and the host-only checks, which run no env-step
 #endif
 #if defined(AW_TASK_TU) && !defined(AW_FAST_MAXDENSE)
 static_assert(AW_FAST_MD == fast_maxdense_of(AW_TASK_TU), "fast_maxdense_of and AW_FAST_MD disagree");
-#elif defined(AW_ONLY_TASK) && !defined(AW_FAST_MAXDENSE)
-static_assert(AW_FAST_MD == fast_maxdense_of(AW_ONLY_TASK), "fast_maxdense_of and AW_FAST_MD disagree");
 #endif
 constexpr int FAST_MAXCON = 48, FAST_NRL = 3, FAST_MAXDENSE = AW_FAST_MD;
 static_assert(FAST_MAXDENSE <= FAST_MAXDENSE_ALLOC, "fast spill blocks are allocated for FAST_MAXDENSE_ALLOC");
@@ -108,7 +106,7 @@ static_assert(EFC_CAP <= MAXEFC && MAXDENSE <= EFC_CAP, "constraint capacities")
 }  // namespace aw
 
 #ifdef AW_STAGE_PROF
-extern __device__ unsigned long long g_stage_prof[];   // adroit_wave.hip (stage profiler builds)
+extern __device__ unsigned long long g_stage_prof[];   // aw_kernels.hip, fast tier (stage profiler builds)
 #endif
 namespace aw {
 constexpr int JSPILL_FAST = (FAST_MAXDENSE_ALLOC - 32) * VS, JSPILL_WIDE = (WIDE_MAXDENSE - 32) * VS;
@@ -177,11 +175,6 @@ static_assert(AW_NPROF_T == 29, "stage profiler slots");
   } while (0)
 #define AW_PROF_COUNT(S, ID) do { if (threadIdx.x == 0) atomicAdd(&::g_stage_prof[ID], 1ull); } while (0)
 #define AW_PROF_ADD(S, ID, V) do { if (threadIdx.x == 0) atomicAdd(&::g_stage_prof[ID], (unsigned long long)(V)); } while (0)
-#elif defined(AW_TRACE)   // debugging builds: every stage boundary printed by lane 0 (device printf)
-#define AW_PROF_START(S) ((void)0)
-#define AW_PROF(S, ID) do { if (threadIdx.x == 0) printf("wg %d stage %d\n", (int)blockIdx.x, (int)(ID)); } while (0)
-#define AW_PROF_COUNT(S, ID) ((void)0)
-#define AW_PROF_ADD(S, ID, V) ((void)0)
 #else
 #define AW_PROF_START(S) ((void)0)
 #define AW_PROF(S, ID) ((void)0)
@@ -473,7 +466,7 @@ constexpr int KIN64_OFF = MAXPAIR * 2;
 static_assert(KIN64_OFF % 16 == 0 && KIN64_OFF + MAXB * 8 * 8 <= JL * VS * 4, "fp64 frames do not fit in the dense-J rows");
 // joint position j in fp64: the env-step's compensated sum qpos + qlo (the fp64 consumers: frames of
 // the MPR / near-margin contact decisions, joint and tendon limit activation)
-// AW_QPOS_COMP (default 0): carry qpos + qlo across the substeps (adroit_wave.hip euler).  Measured
+// AW_QPOS_COMP (default 0): carry qpos + qlo across the substeps (aw_step.h euler).  Measured
 // r06x / r06z: DAPG headline misses 41 -> 13 of 20 480 (0.99937); off by default because one relocate
 // config-3 wide-tier env-step then meets a capsule-box point choice the classifier cannot yet prove a
 // tie.

@@ -1,0 +1,121 @@
+// aw_handle.h -- what the task units (aw_kernels.hip) and the API unit (aw_api.hip) share: the
+// device-side state, the handle behind the C-ABI (include/adroit_wave.h), and the launcher tables
+// through which the API unit reaches the kernels of a task across the link.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/adroit_wave.h"
+#include "aw_common.h"
+
+using namespace aw;
+
+// ---------------------------------------------------------------------------------------
+// device-side state owned by the handle
+struct DState {
+  float* qpos; float* qvel; float* warm; float* params;
+  int* ep_len; float* ep_ret; int* ep_goal; int* episode; unsigned* status;
+  float* last_ret; int* last_goal; int* last_len;
+  unsigned* status_acc;   // OR of every step's flags since create / aw_clear_status (sticky)
+  float* sum_ret;         // sum of the returns of every finished episode
+  int* n_success;         // finished episodes with > success_steps goal steps (evaluate_success)
+};
+
+// the camera and look records of the render kernels (k_depth, k_rgb): host arrays that travel as
+// kernel arguments
+struct CamRec {
+  float c[AW_CAM_FLOATS];
+};
+struct LookRec {
+  float c[AW_LOOK_FLOATS];
+};
+
+struct TaskOps;
+struct WideOps;
+struct aw_handle {
+  int device, nenv, NV;
+  const TaskOps* ops = nullptr;   // the launchers of the model's task, fast and wide tier (aw_create)
+  const WideOps* wide = nullptr;
+  DModel m;
+  DState st;
+  void* dmodel = nullptr;
+  void* dmhdr = nullptr;   // device copy of m (k_step reads its scalars from here)
+  void* dstate = nullptr;
+  int* next_env = nullptr;   // [0, 8): k_step's per-XCD claim counters; [8, 10 + nenv): the wide-tier
+                             // queue (count, claim counter, entries; aw_step.h defer_env);
+                             // [10 + nenv, 10 + 2 nenv): per-env env-step cycles, [10 + 2 nenv,
+                             // 10 + 3 nenv): the claim permutation (k_order)
+  int slots = 0;             // persistent k_step grid: resident workgroups of the selected instantiation,
+                             // or AW_STEP_GRID (read at aw_create; 0 = one workgroup per env)
+  int grid_env = -1;         // AW_STEP_GRID at create (-1: unset)
+  void* dmhdr_wide = nullptr;   // the wide tier's header: m with jspill -> jspill_wide, then st
+  float* jspill_wide = nullptr; // one JSPILL_WIDE block per wide workgroup
+  float* mfac_wide = nullptr;   // one MFAC block per wide workgroup
+  int wide_grid = 0;            // persistent k_step_wide workgroups (resident slots, capped at nenv)
+  // aw_set_fault: the model table's pair margins / broadphase radii as built (restored by kind 0)
+  std::vector<float> fault_margin0, fault_rb0;
+  std::vector<double> fault_margin64_0;
+  std::vector<int> fault_cls;
+  int nsensor = 0;               // the model's sensor count = its sensordata length
+  void* dsens = nullptr;         // the device SensTab (the model table's `sens`)
+  float* sensordata = nullptr;   // aw_set_sensors: [nenv][nsensor], allocated on the first enable
+  bool sensors = false;          // on: the SensTab's `out` points at sensordata and the step launches take the
+                                 // kernels that evaluate the sensors
+  void* ddata = nullptr;         // the device DataTab (the model table's `data`)
+  int data_groups = 0;           // aw_set_data: the AW_DATA_* groups the kernels write (0: off) into the caller's
+                                 // buffers; nonzero selects the step kernels with stage_data
+};
+
+// resident workgroups of a one-wave kernel on the device (occupancy x CUs): a persistent grid
+template <class K>
+static int resident_slots(K kernel, int device) {
+  int per_cu = 0, cus = 0;
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  return std::max(per_cu, 1) * std::max(cus, 1);
+}
+// launch(SENS, DATA) with the handle's switches as compile-time booleans: the step kernels'
+// instantiation that also evaluates the sensors (aw_set_sensors) / writes the mjData views (aw_set_data)
+template <class F>
+static void with_sens_data(const aw_handle* h, F launch) {
+  using T = std::true_type;
+  using N = std::false_type;
+  switch ((h->sensors ? 1 : 0) | (h->data_groups ? 2 : 0)) {
+    case 3: launch(T{}, T{}); break;
+    case 2: launch(N{}, T{}); break;
+    case 1: launch(T{}, N{}); break;
+    default: launch(N{}, N{}); break;
+  }
+}
+
+// The launchers of one task, behind one table: task_ops<TASK> is defined (and with it every
+// fast-tier kernel of TASK instantiated) only in the -DAW_TASK_TU=TASK unit of aw_kernels.hip; the
+// API unit sees the declaration and calls it across the link.
+struct TaskOps {
+  int (*slots)(int device);
+  void (*step)(aw_handle*, const float*, float*, float*, uint8_t*, uint8_t*, float*, int, uint64_t, hipStream_t);
+  void (*reset)(aw_handle*, const uint8_t*, const float*, uint64_t, float*, hipStream_t);
+  void (*set)(aw_handle*, const float*, const float*, const float*, const float*, float*, hipStream_t);
+  void (*dump)(aw_handle*, int, const float*, float*, hipStream_t);
+  void (*depth)(aw_handle*, const CamRec&, int, int, float*, hipStream_t);
+  void (*rgb)(aw_handle*, const CamRec&, const LookRec&, int, int, int, uint8_t*, float*, hipStream_t);
+};
+template <int TASK> const TaskOps* task_ops();
+
+// The wide tier's launcher table, defined in the -DAW_WIDE -DAW_TASK_TU=TASK unit of aw_kernels.hip
+// (k_step_wide<TASK>): `run` drains the queue that the fast launch before it filled.
+struct WideOps {
+  int (*slots)(int device);
+  void (*run)(aw_handle*, const float*, float*, float*, uint8_t*, uint8_t*, float*, int, uint64_t, hipStream_t);
+  void (*dump)(aw_handle*, int, const float*, float*, hipStream_t);   // aw_forward_dump_wide
+};
+template <int TASK> const WideOps* wide_ops();
+
+#ifdef AW_STAGE_PROF
+// The stage profiler's counters (g_stage_prof) live in the fast task unit, whose kernels write them;
+// that unit copies them out (out != nullptr) and zeroes them (reset) for aw_stage_profile.
+hipError_t stage_prof_read(unsigned long long* out, int reset);
+#endif

@@ -1,0 +1,436 @@
+// aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
+// (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
+// -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_dump, k_depth, k_rgb, k_order
+// and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
+// k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
+// env-step both tiers run is aw_step.h.
+#ifndef AW_TASK_TU
+#error "aw_kernels.hip is one task's unit: compile it with -DAW_TASK_TU=<task kind>"
+#endif
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "aw_common.h"
+#include "aw_handle.h"
+#include "aw_render.h"
+#include "aw_step.h"
+
+using namespace aw;
+
+// introspection: one forward of one env, both tiers (aw_forward_dump / aw_forward_dump_wide)
+// dump layout (floats): see mj_envs_amd/_native.py dump_layout (same offsets from the tier's capacities)
+constexpr int DUMP_SCAL = 1760, DUMP_CON = 1768, DUMP_EFC = DUMP_CON + 14 * MAXCON;
+static_assert(DUMP_EFC + 5 * MAXEFC == (WIDE ? AW_DUMP_SIZE_WIDE : AW_DUMP_SIZE), "AW_DUMP_SIZE(_WIDE) out of date");
+// distinct kernel names per tier: the fast and wide units both instantiate it
+#ifdef AW_WIDE
+#define AW_K_DUMP k_dump_wide
+#else
+#define AW_K_DUMP k_dump
+#endif
+template <int TASK>
+__global__ void __launch_bounds__(64) AW_K_DUMP(DModel m, DState st, int env, const float* ctrl, float* out) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  const int lane = threadIdx.x;
+  load_env<NV>(m, s, st, env, lane);
+  if (lane < m.nu) s.ctrl[lane] = ctrl ? ctrl[lane] : 0.f;
+  stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+  float Mrow[NV];
+  Dof d;
+  for (int r = lane; r < MAXEFC; r += 64) out[DUMP_EFC + 4 * MAXEFC + r] = -1.f;
+  forward<TASK, true>(m, s, lane, Mrow, d, out + DUMP_EFC + 4 * MAXEFC);   // + the Newton row states
+  for (int i = lane; i < MAXB * 3; i += 64) out[i] = i < m.nbody * 3 ? (&s.xpos[0][0])[i] : 0.f;
+  for (int i = lane; i < MAXB * 4; i += 64) out[96 + i] = i < m.nbody * 4 ? (&s.xquat[0][0])[i] : 0.f;
+  for (int i = lane; i < MAXS * 3; i += 64) out[224 + i] = i < m.nsite * 3 ? (&s.sxpos[0][0])[i] : 0.f;
+  if (lane < MAXV) {
+    bool v = lane < NV;
+    out[320 + lane] = v ? d.qacc_smooth : 0.f;
+    out[356 + lane] = v ? d.qfrc_smooth : 0.f;
+    out[392 + lane] = v ? d.qacc : 0.f;
+    out[428 + lane] = v ? d.qfrc_con : 0.f;
+  }
+  for (int k = 0; k < NV; k++)
+    if (lane < NV) out[464 + lane * NV + k] = Mrow[k];
+  if (lane == 0) {
+    out[DUMP_SCAL] = (float)s.ncon; out[DUMP_SCAL + 1] = (float)s.nefc; out[DUMP_SCAL + 2] = (float)s.nsparse;
+    out[DUMP_SCAL + 3] = (float)s.ndense; out[DUMP_SCAL + 4] = s.touch[0]; out[DUMP_SCAL + 5] = (float)s.status;
+    out[DUMP_SCAL + 6] = (float)s.it_newton; out[DUMP_SCAL + 7] = (float)s.it_noslip;
+  }
+  for (int c = lane; c < MAXCON; c += 64) {
+    bool v = c < s.ncon;
+    out[DUMP_CON + c] = v ? s.con_dist[c] : 0.f;
+    for (int k = 0; k < 3; k++) out[DUMP_CON + MAXCON + 3 * c + k] = v ? s.con_pos[c][k] : 0.f;
+    float fr[9];
+    for (int k = 0; k < 3; k++) { fr[k] = v ? s.con_nrm[c][k] : 1.f; fr[3 + k] = 0.f; }
+    make_frame(fr);
+    for (int k = 0; k < 9; k++) out[DUMP_CON + 4 * MAXCON + 9 * c + k] = v ? fr[k] : 0.f;
+    out[DUMP_CON + 13 * MAXCON + c] = v ? (float)s.con_pair[c] : -1.f;
+  }
+  for (int r = lane; r < MAXEFC; r += 64) {
+    bool v = r < s.nefc;
+    out[DUMP_EFC + r] = v ? s.efc_force[r] : 0.f;
+    out[DUMP_EFC + MAXEFC + r] = v ? s.efc_aref[r] : 0.f;
+    out[DUMP_EFC + 2 * MAXEFC + r] = v ? s.efc_D[r] : 0.f;
+    out[DUMP_EFC + 3 * MAXEFC + r] = v ? (float)s.efc_type[r] : -1.f;
+  }
+}
+
+#ifdef AW_WIDE
+// The wide tier: persistent workgroups drain the queue the fast launch before it filled (q[0]
+// entries; an empty queue ends every workgroup at its first claim).  Same env-step code with
+// MuJoCo's capacities; mptr is the wide header (its jspill: one JSPILL_WIDE block per workgroup).
+// The claim loop is bounded by the handle's env count (the queue holds at most one entry per env and
+// launch), so every wave reaches its exit whatever the queue words hold; an entry that is not a valid
+// (env < n, kind DK_STEP / DK_FORWARD) pair is skipped -- -DAW_DEVICE_ASSERT traps instead.
+template <int TASK, bool SENS, bool DATA>
+__global__ void __launch_bounds__(64) k_step_wide(const DModel* __restrict__ mptr, const float* __restrict__ actions,
+                                                  float* obs, float* reward, uint8_t* done, uint8_t* goal,
+                                                  float* terminal_obs, int autoreset, uint64_t seed,
+                                                  int* __restrict__ q, int n) {
+  const DModel& m = *mptr;
+  const DState& st = *reinterpret_cast<const DState*>(mptr + 1);
+  __shared__ Env s;
+  __shared__ StepIO io;
+  const int lane = threadIdx.x;
+  park_io(io, lane, actions, obs, reward, done, goal, terminal_obs, autoreset, seed, nullptr);
+  for (int claims = 0; claims <= n; claims++) {
+    int k = 0;
+    if (lane == 0) k = atomicAdd(q + 1, 1);
+    k = __builtin_amdgcn_readfirstlane(k);
+    const int nq = q[0];
+#ifdef AW_DEVICE_ASSERT
+    if ((unsigned)nq > (unsigned)n) __builtin_trap();
+#endif
+    if (k >= nq || k >= n) break;
+    const int ent = q[2 + k];
+    const int env = ent & 0x3fffffff, kind = ent >> 30;
+    if ((unsigned)env >= (unsigned)n || kind > DK_FORWARD) {
+#ifdef AW_DEVICE_ASSERT
+      __builtin_trap();
+#endif
+      continue;
+    }
+    env_step<TASK, SENS, DATA>(m, s, st, env, lane, io, kind);
+  }
+}
+
+template <int TASK>
+static void launch_wide(aw_handle* h, const float* a, float* obs, float* rew, uint8_t* done, uint8_t* goal,
+                        float* tobs, int autoreset, uint64_t seed, hipStream_t st) {
+  with_sens_data(h, [&](auto S, auto D) {
+    hipLaunchKernelGGL((k_step_wide<TASK, decltype(S)::value, decltype(D)::value>), dim3(h->wide_grid), dim3(64), 0, st,
+                       (const DModel*)h->dmhdr_wide, a, obs, rew, done, goal, tobs, autoreset, seed, h->next_env + 8, h->nenv);
+  });
+}
+template <int TASK>
+static void launch_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, hipStream_t st) {
+  DModel mw = h->m;
+  mw.jspill = h->jspill_wide;   // the dense rows past JL in the wide tier's spill block (slot 0)
+  mw.mfac = h->mfac_wide;
+  hipLaunchKernelGGL((k_dump_wide<TASK>), dim3(1), dim3(64), 0, st, mw, h->st, env, ctrl, out);
+}
+template <int TASK> const WideOps* wide_ops() {
+  static const WideOps ops = {[](int device) { return resident_slots(k_step_wide<TASK, false, false>, device); },
+                              launch_wide<TASK>, launch_dump_wide<TASK>};
+  return &ops;
+}
+template const WideOps* wide_ops<AW_TASK_TU>();
+
+#else  // the fast tier
+
+#ifdef AW_STAGE_PROF
+// the stage profiler's counters, next to the kernels that write them, and their way out
+__device__ unsigned long long g_stage_prof[AW_NPROF];
+hipError_t stage_prof_read(unsigned long long* out, int reset) {
+  hipError_t e = hipSuccess;
+  if (out) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stage_prof), sizeof(unsigned long long) * AW_NPROF);
+  if (reset && e == hipSuccess) {
+    unsigned long long z[AW_NPROF] = {};
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_stage_prof), z, sizeof(z));
+  }
+  return e;
+}
+#endif
+
+// The next env for a persistent k_step workgroup, XCD-aware.  Workgroups b and b + 8 share an XCD
+// (round-robin dispatch, MI355X_MICROARCH.md -- for speed only, correctness never depends on it),
+// so workgroup class c = b % 8 owns envs [n c / 8, n (c + 1) / 8): its first round takes the class's
+// first gridDim.x / 8 envs, the rest are claimed from the class's own counter.  Neighbouring envs,
+// whose rows share 32-byte sectors (state and obs rows, the 1- and 4-byte per-env scalars), are then
+// written through ONE L2, where the partial sectors merge before write-back: k_step's HBM traffic
+// 1.81 -> 1.30 KB per env-step (r04p, raw counters).  A class whose range is exhausted claims from
+// the next classes, so the tail stays balanced.  Returns n when every class is exhausted.
+AW_DEV int claim_env(int* next_env, int n, int lane) {
+  const int c0 = blockIdx.x & 7, share = gridDim.x >> 3;
+  for (int t = 0; t < 8; t++) {
+    const int c = (c0 + t) & 7;
+    const int lo = (int)((long long)n * c / 8), hi = (int)((long long)n * (c + 1) / 8);
+    if (lo + share >= hi) continue;   // the class's first round covered it
+    int k = 0;
+    if (lane == 0) k = atomicAdd(next_env + c, 1);
+    // readfirstlane: env stays a scalar (SGPR addresses, no per-lane pointer spills)
+    const int e = lo + share + __builtin_amdgcn_readfirstlane(k);
+    if (e < hi) return e;
+  }
+  return n;
+}
+
+// One launch = one env-step of every env (fast tier).  next_env[0..7]: the per-XCD claim
+// counters, next_env[8..]: the wide-tier queue (defer_env).  One kernel per (task, sensors, data).
+template <int TASK, bool SENS, bool DATA>
+__global__ void __launch_bounds__(64) AW_KSTEP_ATTR k_step(DModel mval, const DModel* __restrict__ mptr, DState stval,
+                                             int n, const float* __restrict__ actions,
+                                             float* obs, float* reward, uint8_t* done, uint8_t* goal,
+                                             float* terminal_obs, int autoreset, uint64_t seed,
+                                             int* __restrict__ next_env) {
+  // model scalars read from the device copy on demand (scalar loads behind the loop's memory
+  // clobber) instead of ~50 kernel-argument SGPRs held live across the whole launch
+  const DModel& m = *mptr;
+  (void)mval;
+  // the state pointers read from the device header where they are used (the loop's memory
+  // clobber forces the reload) instead of ~30 SGPRs of kernel arguments live across the launch
+  const DState& st = *reinterpret_cast<const DState*>(mptr + 1);   // DState follows DModel in the header
+  (void)stval;
+  __shared__ Env s;
+  __shared__ StepIO io;
+  const int lane = threadIdx.x;
+  park_io(io, lane, actions, obs, reward, done, goal, terminal_obs, autoreset, seed, next_env + 8);
+  const bool xmap = (int)gridDim.x < n && (gridDim.x & 7) == 0;
+  // claim positions map to envs through k_order's permutation (same XCD class, costliest first:
+  // the launch's last claims are its cheapest envs, r05 A/B -0.3 % random, -2.9 % DAPG)
+  if (lane == 0) {
+    io.cost = xmap ? reinterpret_cast<unsigned*>(next_env + 10 + n) : nullptr;
+    io.perm = xmap ? next_env + 10 + 2 * n : nullptr;
+  }
+  wsync();
+  auto env_of = [&](int pos) {
+    if (!io.perm) return pos;
+    const int e = io.perm[pos];
+    return (unsigned)e < (unsigned)n ? e : pos;
+  };
+  // Persistent workgroups: the grid is one workgroup per resident slot (launch_step); each takes
+  // a first env, then the next unclaimed ones from the launch's counters, so the per-slot spill
+  // block (s.slot) is rewritten in the XCD's L2 instead of streaming a per-env block to memory.
+  // Envs go out in XCD-contiguous ranges (claim_env above); grids that are not a multiple of 8
+  // workgroups (AW_STEP_GRID) take env blockIdx.x first and then claim from one counter.  Every
+  // workgroup exits once the counters pass n.
+  int env = xmap ? (int)((long long)n * (blockIdx.x & 7) / 8) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  if (xmap && env >= (int)((long long)n * ((blockIdx.x & 7) + 1) / 8)) env = claim_env(next_env, n, lane);
+  while (env < n) {
+    env_step<TASK, SENS, DATA>(m, s, st, env_of(env), lane, io);
+    if ((int)gridDim.x >= n) break;            // one env per workgroup: no counter
+    int claim = 0;
+    if (xmap) {
+      env = claim_env(next_env, n, lane);
+      continue;
+    }
+    if (lane == 0) claim = atomicAdd(next_env, 1);
+    // readfirstlane, not a shuffle: env stays a scalar, so the addresses formed from it are
+    // SGPR values instead of per-lane 64-bit VGPR pairs spilled to scratch once per env
+    env = (int)gridDim.x + __builtin_amdgcn_readfirstlane(claim);
+  }
+}
+
+template <int TASK>
+__global__ void __launch_bounds__(64) k_reset(DModel m, DState st, int n, const uint8_t* mask,
+                                              const float* params, uint64_t seed, float* obs, int* defer) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  const int env = blockIdx.x, lane = threadIdx.x;
+  if (env >= n) return;
+  if (mask && !mask[env]) return;
+  if (lane == 0) { s.status = 0u; s.slot = blockIdx.x; }
+  reset_prepare<NV>(m, s, st, env, lane, params, seed);
+  float Mrow[NV];
+  Dof d;
+  forward<TASK>(m, s, lane, Mrow, d);
+  store_env<NV>(m, s, st, env, lane);
+  if (fast_overflow(m, s)) {
+    if (lane == 0) { st.status[env] = s.status & ~ST_OVF; st.status_acc[env] |= s.status & ~ST_OVF; }
+    defer_env(defer, env, DK_FORWARD, lane);
+    return;
+  }
+  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
+  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
+  if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
+  if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
+}
+
+template <int TASK>
+__global__ void __launch_bounds__(64) k_set_state(DModel m, DState st, int n, const float* qpos,
+                                                  const float* qvel, const float* warm,
+                                                  const float* params, float* obs, int* defer) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  const int env = blockIdx.x, lane = threadIdx.x;
+  if (env >= n) return;
+  load_env<NV>(m, s, st, env, lane);
+  if (lane < NV) {
+    if (qpos) s.qpos[lane] = qpos[(size_t)env * m.nq + lane];
+    if (qvel) s.qvel[lane] = qvel[(size_t)env * m.nv + lane];
+    if (warm) s.warm[lane] = warm[(size_t)env * m.nv + lane];
+  }
+  if (params && lane < m.nparam) st.params[(size_t)env * m.nparam + lane] = params[(size_t)env * m.nparam + lane];
+  __threadfence_block();
+  wsync();
+  if (lane < m.nu) s.ctrl[lane] = 0.f;
+  stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+  float Mrow[NV];
+  Dof d;
+  forward<TASK>(m, s, lane, Mrow, d);
+  store_env<NV>(m, s, st, env, lane);
+  if (fast_overflow(m, s)) {
+    if (lane == 0) { st.status[env] = s.status & ~ST_OVF; st.status_acc[env] |= s.status & ~ST_OVF; }
+    defer_env(defer, env, DK_FORWARD, lane);
+    return;
+  }
+  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
+  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
+  if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
+  if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
+}
+
+// depth frame of every env's current state: wave 0 runs the kinematics, then all four waves
+// cast the pixels (one workgroup per env; render geom poses staged in LDS)
+template <int TASK>
+__global__ void __launch_bounds__(256) k_depth(DModel m, DState st, int n, CamRec cam, int W, int H, float* out) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RGeoms rg;
+  const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (env >= n) return;
+  if (tid < 64) {
+    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+    wsync();
+    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+    stage_kinematics(m, s, lane);
+  }
+  __syncthreads();
+  render_geoms(m, s, rg, cam.c, tid, 256);
+  __syncthreads();
+  float* o = out + (size_t)env * W * H;
+  for (int p0 = (tid >> 6) * 64; p0 < W * H; p0 += 256) render_span(rg, m.nrgeom, cam.c, W, H, p0, lane, o);
+}
+
+// colour frame (and optionally the aligned depth frame) of every env's current state: k_depth's
+// structure, with the visible sites, the env's colour table and the lights staged next to the
+// geom poses; each wave shades 64-pixel spans (aw_render.h render_span_rgb)
+template <int TASK>
+__global__ void __launch_bounds__(256) k_rgb(DModel m, DState st, int n, CamRec cam, LookRec look, int W, int H, int ss,
+                                             unsigned char* out, int dwords, float* depth) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RGeoms rg;
+  __shared__ RColors rc;
+  const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (env >= n) return;
+  if (tid < 64) {
+    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+    wsync();
+    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+    stage_kinematics(m, s, lane);
+  }
+  __syncthreads();
+  render_geoms(m, s, rg, cam.c, tid, 256);
+  render_sites(m, s, rg, cam.c, tid, 256);
+  render_colors(m, s, rc, cam.c, look.c, tid, 256);
+  __syncthreads();
+  unsigned char* o = out + (size_t)env * W * H * 3;
+  float* z = depth ? depth + (size_t)env * W * H : nullptr;
+  for (int p0 = (tid >> 6) * 64; p0 < W * H; p0 += 256)
+    render_span_rgb(rg, rc, m.nrgeom, m.nrsite, cam.c, look.c, W, H, ss, p0, lane, tid >> 6, o, dwords != 0, z);
+}
+
+// Claim order for the next k_step launch (longest processing time first): per XCD class c (k_step's
+// env range [n c / 8, n (c + 1) / 8)) the envs are bucketed by their last env-step's shader cycles
+// on a quarter-octave scale and written costliest bucket first into perm (positions of the same
+// range), so the launch's last claims are its cheapest envs.  One workgroup per class.
+static __device__ int cost_bucket(unsigned c) {
+  if (c < (1u << 16)) return 0;
+  const int e = 31 - __clz(c);                       // floor(log2 c) >= 16
+  const int key = 4 * e + (int)((c >> (e - 2)) & 3);  // quarter octaves
+  const int b = key - 4 * 16;
+  return b > 63 ? 63 : b;
+}
+static __global__ void __launch_bounds__(1024) k_order(const unsigned* __restrict__ cost, int* __restrict__ perm, int n) {
+  const int c = blockIdx.x;
+  const int lo = (int)((long long)n * c / 8), hi = (int)((long long)n * (c + 1) / 8);
+  __shared__ int hist[64];
+  if (threadIdx.x < 64) hist[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = lo + (int)threadIdx.x; i < hi; i += blockDim.x) atomicAdd(&hist[cost_bucket(cost[i])], 1);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int acc = 0;
+    for (int b = 63; b >= 0; b--) { const int h = hist[b]; hist[b] = acc; acc += h; }
+  }
+  __syncthreads();
+  for (int i = lo + (int)threadIdx.x; i < hi; i += blockDim.x) {
+    const int k = atomicAdd(&hist[cost_bucket(cost[i])], 1);
+    perm[lo + k] = i;
+  }
+}
+
+// every launch that runs a fast-tier forward clears the wide queue first and drains it after
+static void clear_queue(aw_handle* h, bool counters, hipStream_t st) {
+  if (counters) (void)hipMemsetAsync(h->next_env, 0, 10 * sizeof(int), st);   // XCD counters + queue heads
+  else (void)hipMemsetAsync(h->next_env + 8, 0, 2 * sizeof(int), st);
+}
+template <int TASK>
+static void launch_step(aw_handle* h, const float* a, float* obs, float* rew, uint8_t* done, uint8_t* goal,
+                        float* tobs, int autoreset, uint64_t seed, hipStream_t st) {
+  // grid = the handle's persistent slot count (aw_create / aw_set_option), capped at nenv
+  const int grid = std::min(h->nenv, h->slots);
+  clear_queue(h, grid < h->nenv, st);
+  if (grid < h->nenv && (grid & 7) == 0)   // the XCD-class claim path (k_step xmap)
+    hipLaunchKernelGGL(k_order, dim3(8), dim3(1024), 0, st, reinterpret_cast<const unsigned*>(h->next_env + 10 + h->nenv),
+                       h->next_env + 10 + 2 * h->nenv, h->nenv);
+  with_sens_data(h, [&](auto S, auto D) {
+    hipLaunchKernelGGL((k_step<TASK, decltype(S)::value, decltype(D)::value>), dim3(grid), dim3(64), 0, st, h->m,
+                       (const DModel*)h->dmhdr, h->st, h->nenv, a, obs, rew, done, goal, tobs, autoreset, seed, h->next_env);
+  });
+  wide_ops<TASK>()->run(h, a, obs, rew, done, goal, tobs, autoreset, seed, st);
+}
+template <int TASK>
+static void launch_reset(aw_handle* h, const uint8_t* mask, const float* params, uint64_t seed, float* obs,
+                         hipStream_t st) {
+  clear_queue(h, false, st);
+  hipLaunchKernelGGL((k_reset<TASK>), dim3(h->nenv), dim3(64), 0, st, h->m, h->st, h->nenv, mask, params, seed, obs,
+                     h->next_env + 8);
+  wide_ops<TASK>()->run(h, nullptr, obs, nullptr, nullptr, nullptr, nullptr, 0, seed, st);
+}
+template <int TASK>
+static void launch_set(aw_handle* h, const float* q, const float* v, const float* w, const float* p, float* obs,
+                       hipStream_t st) {
+  clear_queue(h, false, st);
+  hipLaunchKernelGGL((k_set_state<TASK>), dim3(h->nenv), dim3(64), 0, st, h->m, h->st, h->nenv, q, v, w, p, obs,
+                     h->next_env + 8);
+  wide_ops<TASK>()->run(h, nullptr, obs, nullptr, nullptr, nullptr, nullptr, 0, 0, st);
+}
+template <int TASK>
+static void launch_dump(aw_handle* h, int env, const float* ctrl, float* out, hipStream_t st) {
+  hipLaunchKernelGGL((k_dump<TASK>), dim3(1), dim3(64), 0, st, h->m, h->st, env, ctrl, out);
+}
+
+template <int TASK>
+static void launch_depth(aw_handle* h, const CamRec& cam, int W, int H, float* out, hipStream_t st) {
+  hipLaunchKernelGGL((k_depth<TASK>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, cam, W, H, out);
+}
+template <int TASK>
+static void launch_rgb(aw_handle* h, const CamRec& cam, const LookRec& look, int W, int H, int ss, uint8_t* rgb,
+                       float* depth, hipStream_t st) {
+  // whole-dword stores need a frame size and a base that are multiples of 4 bytes
+  const int dwords = (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;
+  hipLaunchKernelGGL((k_rgb<TASK>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, cam, look, W, H, ss, rgb,
+                     dwords, depth);
+}
+template <int TASK> const TaskOps* task_ops() {
+  static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
+                              launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
+                              launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>};
+  return &ops;
+}
+template const TaskOps* task_ops<AW_TASK_TU>();
+#endif  // AW_WIDE

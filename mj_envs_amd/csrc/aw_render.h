@@ -6,6 +6,7 @@
 // (geometry), tests/rgb_checker.py (colour).
 #pragma once
 #include "aw_common.h"
+#include "aw_dynamics.h"
 #include "aw_solver.h"
 
 namespace aw {

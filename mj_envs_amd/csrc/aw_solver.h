@@ -14,6 +14,7 @@
 //     update is fma -> med3 -> readlane -> fma on the serial chain.
 #pragma once
 #include "aw_common.h"
+#include "aw_dynamics.h"
 #include "aw_tree.h"
 
 namespace aw {

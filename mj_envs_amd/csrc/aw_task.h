@@ -122,6 +122,14 @@ AW_DEV void task_obs(const DModel& m, Env& s, int lane, float* out) {
   }
 }
 
+// the observation through s.rowbuf to global memory (the env-step and aw_task_eval's kernel)
+AW_DEV void write_obs(const DModel& m, Env& s, int lane, float* out) {
+  task_obs(m, s, lane, s.rowbuf);
+  wsync();
+  for (int o = lane; o < m.obs_dim; o += 64) GOUT(out)[o] = s.rowbuf[o];
+  wsync();
+}
+
 // lane 0 computes reward / done / goal (fp32 restatement of the reference arithmetic)
 AW_DEV void task_reward(const DModel& m, Env& s, float* reward, int* done, int* goal) {
   const int* id = m.d->task_idx;

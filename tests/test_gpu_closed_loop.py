@@ -151,7 +151,7 @@ def test_shards_bitwise_equal_to_one_batch(env_id):
 @pytest.mark.parametrize("n", [2049, 6149, 16387])
 def test_persistent_claims_cover_every_env_once(n):
     """k_step's persistent grid hands envs out in XCD-contiguous ranges with per-class counters
-    and stealing (adroit_wave.hip claim_env): with env counts that split unevenly over the eight
+    and stealing (aw_kernels.hip claim_env): with env counts that split unevenly over the eight
     classes, every env is stepped exactly once per launch (ep_len) and the states equal, bit for
     bit, a launch with one workgroup per env (AW_STEP_GRID=0) and one with an odd grid of 1 001
     workgroups on the single-counter path."""

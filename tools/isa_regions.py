@@ -4,7 +4,7 @@
 
 Compiles the device code with -g, attributes every instruction of k_step<TASK> to its source
 line (.loc; inlined code keeps its own file / line) and sums the counts per enclosing function of
-mj_envs_amd/csrc/*.h / adroit_wave.hip: VALU, SALU, LDS, VMEM, scratch, readlane / writelane and
+mj_envs_amd/csrc/*.h / aw_kernels.hip: VALU, SALU, LDS, VMEM, scratch, readlane / writelane and
 s_nop.  Together with the stage profile (cycles per stage) it says which stages are issue-heavy
 and which are latency-bound.
 """
@@ -16,7 +16,7 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-from __graft_entry__ import HIPCC_FLAGS, HIP_SRC  # noqa: E402
+from __graft_entry__ import HIPCC_FLAGS, KERNELS_SRC  # noqa: E402
 
 FUNC = re.compile(r"^(?:template\s*<[^>]*>\s*)?(?:AW_DEV|__global__|static)[^;{]*?\b(\w+)\s*\(", re.M)
 
@@ -64,8 +64,8 @@ def main():
     extra = sys.argv[2:]
     out = "/tmp/isa_regions.s"
     flags = [f for f in HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-g", "-S", "--cuda-device-only", f"-DAW_ONLY_TASK={task}", *extra,
-                    "-o", out, HIP_SRC], check=True)
+    subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-g", "-S", "--cuda-device-only", f"-DAW_TASK_TU={task}", *extra,
+                    "-o", out, KERNELS_SRC], check=True)
     text = open(out).read().splitlines()
     files = {}
     for l in text:

@@ -17,13 +17,15 @@ PROF_LIB = os.path.join(REPO, "mj_envs_amd", "libadroit_hip_prof.so")
 
 
 def build(task: int = 0):
-    """one-TU profiling build of the fast tier + the task's wide-tier object (no markers there)"""
+    """profiling build of one task: its fast-tier unit with the stage markers (and their counters),
+    its wide-tier unit (no markers there) and the C-ABI holding that one task"""
     sys.path.insert(0, REPO)
-    from __graft_entry__ import HIPCC_FLAGS, compile_units, hipcc_path, wide_unit
+    from __graft_entry__ import API_SRC, KERNELS_SRC, compile_units, hipcc_path, wide_unit
     objdir = os.path.join(REPO, "build", "hip")
     os.makedirs(objdir, exist_ok=True)
-    prof_o = os.path.join(objdir, "prof_fast.o")
-    units = [(f"-DAW_STAGE_PROF -DAW_ONLY_TASK={task}", prof_o), wide_unit(task, objdir, "prof")]
+    units = [(f"-DAW_STAGE_PROF -DAW_TASK_TU={task}", os.path.join(objdir, "prof_fast.o"), KERNELS_SRC),
+             wide_unit(task, objdir, "prof"),
+             (f"-DAW_STAGE_PROF -DAW_ONLY_TASK={task}", os.path.join(objdir, "prof_api.o"), API_SRC)]
     compile_units(units)
     subprocess.run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PROF_LIB,
                     *[u[1] for u in units]], check=True)
