@@ -282,6 +282,31 @@ int aw_render_depth(aw_handle* h, const float* cam, int width, int height, float
 int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, int height, int ss,
                   uint8_t* rgb, float* depth, void* stream);
 
+/* Cameras in the frame of a body, one per env, several per launch.  One launch renders every view
+ * of every env's current state: the model is staged and the kinematics run once per env, then each
+ * view's world record is composed and its frame ray-cast as aw_render_rgb / aw_render_depth do.
+ *   views: HOST array of nviews (1..AW_MAX_VIEWS) records, each the AW_CAM_FLOATS layout of
+ * aw_render_depth expressed in the frame of body `body` (0 = the world): the models' own <camera>s,
+ * a camera mounted on a moving body such as the palm, or the free camera
+ * (mj_envs_amd/render.py model_camera / mounted_camera / free_camera).  A record of body 0 is used
+ * as it is.  For body b > 0 the kernel composes the world record in fp32 from the env's body frames:
+ * position xpos[b] + rot(xquat[b], pos), the three axes rotated by xquat[b], the five scalars copied.
+ *   env_cam: NULL, or DEVICE [N][nviews][AW_CAM_FLOATS]: env e renders view v from env_cam[e][v]
+ * in place of views[v].rec (camera randomisation; the body is still views[v].body).  A per-env
+ * record is not validated: whatever it holds, the kernel writes only that env's own frames.
+ *   rgb: DEVICE [N][nviews][height][width][3] uint8 or NULL; depth: DEVICE [N][nviews][height][width]
+ * or NULL.  Shading, sites, tints, look and ss are aw_render_rgb's, with the headlight at the
+ * composed camera position.  With rgb == NULL the call is depth-only (ss must be 1) and needs no
+ * appearance arrays.  One view of body 0 without env_cam writes bit for bit the frames of
+ * aw_render_rgb (rgb != NULL) / aw_render_depth (rgb == NULL).
+ * AW_EINVAL: nviews outside 1..AW_MAX_VIEWS, a body outside [0, nbody), both outputs NULL, ss not 1
+ * or 2, depth or a NULL rgb with ss 2, sizes <= 0 or > 1024.  AW_EUNSUPPORTED: rgb != NULL on a
+ * model table without the appearance arrays. */
+#define AW_MAX_VIEWS 4
+typedef struct { float rec[AW_CAM_FLOATS]; int32_t body; } aw_view;
+int aw_render_views(aw_handle* h, const aw_view* views, int nviews, const float* env_cam, const float* look,
+                    int width, int height, int ss, uint8_t* rgb, float* depth, void* stream);
+
 /* On-device Gaussian MLP policy: mjrl gaussian_mlp.MLP as used by the
  * reference's DAPG baseline (algos/baselines.py:67-86, hidden_sizes=(32, 32)) -- two tanh
  * hidden layers of width `hidden` (32 or 64), in/out affine transforms, and with sample != 0

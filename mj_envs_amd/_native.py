@@ -68,6 +68,14 @@ class DataBufs(ctypes.Structure):
     _fields_ = [(k, _vp) for k in ("xpos", "xquat", "site_xpos", "qacc", "qfrc_constraint", "counts", "contact")]
 
 
+AW_MAX_VIEWS = 4
+
+
+class View(ctypes.Structure):
+    """aw_view: a camera record in the frame of a body (0: the world)"""
+    _fields_ = [("rec", ctypes.c_float * 17), ("body", ctypes.c_int32)]
+
+
 def data_groups(data) -> int:
     """AW_DATA_* mask of ``data``: False / None -> 0, True -> every group, a group name or an
     iterable of them ("kin", "dyn", "contact"), or the mask itself"""
@@ -149,6 +157,10 @@ def load():
     if hasattr(L, "aw_render_rgb"):
         L.aw_render_rgb.argtypes = [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]
         L.aw_render_rgb.restype = ctypes.c_int
+    if hasattr(L, "aw_render_views"):
+        L.aw_render_views.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, _vp, _vp, _vp]
+        L.aw_render_views.restype = ctypes.c_int
     if hasattr(L, "aw_policy_mlp"):
         L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, _vp]
@@ -168,7 +180,7 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
            "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_render_rgb",
-           "aw_policy_mlp",
+           "aw_render_views", "aw_policy_mlp",
            "aw_collide_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
@@ -419,6 +431,39 @@ class Sim:
             assert lk.size == 7, "render_rgb: look record has 7 floats"
         _check(load().aw_render_rgb(self.h, c.ctypes.data, None if lk is None else lk.ctypes.data, w, h, int(ss),
                                     _ptr(out), _ptr(depth), _stream()))
+
+    def render_views(self, views, width: int, height: int, rgb=None, depth=None, env_cam=None,
+                     look: Optional[np.ndarray] = None, ss: int = 1):
+        """Every view of every env's current state in one launch (include/adroit_wave.h
+        aw_render_views).  views: a list of (record, body) pairs -- a 17-float host camera record in
+        the frame of body ``body`` (0: the world; mj_envs_amd.render model_camera / mounted_camera,
+        or (free_camera(...), 0)); rgb [N, V, H, W, 3] (device, uint8) and / or depth [N, V, H, W]
+        (device, fp32; ss must be 1); env_cam [N, V, 17] (device, fp32): per-env records used in
+        place of the views' own; look as in render_rgb."""
+        import torch
+        nv = len(views)
+        n, w, h = self.n_envs, int(width), int(height)
+        arr = (View * max(nv, 1))()
+        for k, (rec, body) in enumerate(views):
+            c = np.ascontiguousarray(rec, np.float32)
+            assert c.size == 17, "render_views: a camera record has 17 floats"
+            arr[k].rec[:] = c.ravel().tolist()
+            arr[k].body = int(body)
+        if rgb is not None:
+            assert tuple(rgb.shape) == (n, nv, h, w, 3) and rgb.dtype == torch.uint8 and rgb.is_contiguous(), \
+                "render_views: rgb must be uint8 [n_envs, V, H, W, 3]"
+        if depth is not None:
+            assert tuple(depth.shape) == (n, nv, h, w) and depth.dtype == torch.float32 and depth.is_contiguous(), \
+                "render_views: depth must be fp32 [n_envs, V, H, W]"
+        if env_cam is not None:
+            assert tuple(env_cam.shape) == (n, nv, 17) and env_cam.dtype == torch.float32 and \
+                env_cam.is_contiguous(), "render_views: env_cam must be fp32 [n_envs, V, 17]"
+        lk = None
+        if look is not None:
+            lk = np.ascontiguousarray(look, np.float32)
+            assert lk.size == 7, "render_views: look record has 7 floats"
+        _check(load().aw_render_views(self.h, arr, nv, _ptr(env_cam), None if lk is None else lk.ctypes.data, w, h,
+                                      int(ss), _ptr(rgb), _ptr(depth), _stream()))
 
     def collide_test(self, types, pos, mat, size, margin, fp64: bool = False):
         """narrowphase of n primitive pairs (test hook): list of arrays [(dist, pos[3], normal[3]), ...]

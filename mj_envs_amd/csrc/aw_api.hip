@@ -591,6 +591,29 @@ int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, 
   return AW_OK;
 }
 
+int aw_render_views(aw_handle* h, const aw_view* views, int nviews, const float* env_cam, const float* look, int width,
+                    int height, int ss, uint8_t* rgb, float* depth, void* stream) {
+  if (!h || !views || nviews < 1 || nviews > AW_MAX_VIEWS || (!rgb && !depth) || width <= 0 || height <= 0 ||
+      width > 1024 || height > 1024 || (ss != 1 && ss != 2) || (ss != 1 && (depth || !rgb)))
+    return fail(AW_EINVAL, "aw_render_views: bad arguments");
+  for (int v = 0; v < nviews; v++)
+    if (views[v].body < 0 || views[v].body >= h->m.nbody)
+      return fail(AW_EINVAL, "aw_render_views: a view's body is not a body of the model");
+  if (rgb && !h->m.appearance)
+    return fail(AW_EUNSUPPORTED, "aw_render_views: the model table carries no appearance arrays");
+  HIPCHK(hipSetDevice(h->device));
+  ViewsRec r = {};
+  for (int v = 0; v < nviews; v++) {
+    memcpy(r.c[v], views[v].rec, sizeof(r.c[v]));   // host array: the records travel as a kernel argument
+    r.body[v] = views[v].body;
+  }
+  LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
+  if (look) memcpy(l.c, look, sizeof(l.c));
+  h->ops->views(h, r, nviews, env_cam, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
 int aw_policy_mlp(int n, int in_dim, int hidden, int out_dim, const float* params, const float* obs, float* act,
                   int sample, uint64_t seed, uint64_t step, uint64_t env_offset, void* stream) {
   if (n <= 0 || !params || !obs || !act || in_dim <= 0 || in_dim > MLP_IMAX || out_dim <= 0 || out_dim > MLP_OMAX)

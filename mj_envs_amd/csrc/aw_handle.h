@@ -24,13 +24,18 @@ struct DState {
   int* n_success;         // finished episodes with > success_steps goal steps (evaluate_success)
 };
 
-// the camera and look records of the render kernels (k_depth, k_rgb): host arrays that travel as
+// the camera and look records of the render kernels (k_depth, k_rgb, k_views): host arrays that travel as
 // kernel arguments
 struct CamRec {
   float c[AW_CAM_FLOATS];
 };
 struct LookRec {
   float c[AW_LOOK_FLOATS];
+};
+// the views of one aw_render_views launch (k_views): each record in the frame of its body
+struct ViewsRec {
+  float c[AW_MAX_VIEWS][AW_CAM_FLOATS];
+  int body[AW_MAX_VIEWS];
 };
 
 struct TaskOps;
@@ -102,6 +107,8 @@ struct TaskOps {
   void (*dump)(aw_handle*, int, const float*, float*, hipStream_t);
   void (*depth)(aw_handle*, const CamRec&, int, int, float*, hipStream_t);
   void (*rgb)(aw_handle*, const CamRec&, const LookRec&, int, int, int, uint8_t*, float*, hipStream_t);
+  void (*views)(aw_handle*, const ViewsRec&, int, const float*, const LookRec&, int, int, int, uint8_t*, float*,
+                hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 

@@ -1,7 +1,7 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
-// -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_dump, k_depth, k_rgb, k_order
-// and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
+// -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_dump, k_depth, k_rgb, k_views,
+// k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
 // k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
 // env-step both tiers run is aw_step.h.
 #ifndef AW_TASK_TU
@@ -343,6 +343,60 @@ __global__ void __launch_bounds__(256) k_rgb(DModel m, DState st, int n, CamRec 
     render_span_rgb(rg, rc, m.nrgeom, m.nrsite, cam.c, look.c, W, H, ss, p0, lane, tid >> 6, o, dwords != 0, z);
 }
 
+// several cameras per launch, each in the frame of a body, optionally one record per env and view
+// (aw_render_views): k_rgb's (RGB) or k_depth's structure with the staging and the kinematics done
+// once per env, then per view the world record composed into LDS (compose_view), the pixel boxes
+// and the headlight rebuilt against it and the spans cast.  The aw_render.h functions are the ones
+// k_depth / k_rgb call, so a world-frame view writes their frames bit for bit.  Every barrier of
+// the view loop is uniform: nviews is a kernel argument and the early return takes the whole block.
+// dwords: every frame's base and size are multiples of 4 bytes (launch_views).
+struct NoColors {};
+template <int TASK, bool RGB>
+__global__ void __launch_bounds__(256) k_views(DModel m, DState st, int n, ViewsRec views, int nviews,
+                                               const float* __restrict__ env_cam, LookRec look, int W, int H, int ss,
+                                               unsigned char* out, int dwords, float* depth) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RGeoms rg;
+  __shared__ std::conditional_t<RGB, RColors, NoColors> rc;
+  __shared__ float lcam[AW_CAM_FLOATS];
+  const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (env >= n) return;
+  if (tid < 64) {
+    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+    wsync();
+    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+    stage_kinematics(m, s, lane);
+  }
+  __syncthreads();
+  if constexpr (RGB) render_colors_env(m, s, rc, look.c, tid, 256);
+  const size_t np = (size_t)W * H;
+  for (int v = 0; v < nviews; v++) {
+    const size_t frame = (size_t)env * nviews + v;
+    compose_view(s, env_cam ? env_cam + frame * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid);
+    __syncthreads();
+    // the record is uniform over the block: held in scalar registers, as k_rgb's kernel argument is
+    float cam[AW_CAM_FLOATS];
+    for (int k = 0; k < AW_CAM_FLOATS; k++)
+      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    render_geoms(m, s, rg, cam, tid, 256);
+    if constexpr (RGB) {
+      render_sites(m, s, rg, cam, tid, 256);
+      render_headlight(rc, cam, look.c, tid);
+    }
+    __syncthreads();
+    float* z = depth ? depth + frame * np : nullptr;
+    for (int p0 = (tid >> 6) * 64; p0 < W * H; p0 += 256) {
+      if constexpr (RGB)
+        render_span_rgb(rg, rc, m.nrgeom, m.nrsite, cam, look.c, W, H, ss, p0, lane, tid >> 6, out + frame * np * 3,
+                        dwords != 0, z);
+      else
+        render_span(rg, m.nrgeom, cam, W, H, p0, lane, z);
+    }
+    __syncthreads();   // the next view overwrites cam, the boxes and the headlight
+  }
+}
+
 // Claim order for the next k_step launch (longest processing time first): per XCD class c (k_step's
 // env range [n c / 8, n (c + 1) / 8)) the envs are bucketed by their last env-step's shader cycles
 // on a quarter-octave scale and written costliest bucket first into perm (positions of the same
@@ -426,10 +480,24 @@ static void launch_rgb(aw_handle* h, const CamRec& cam, const LookRec& look, int
   hipLaunchKernelGGL((k_rgb<TASK>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, cam, look, W, H, ss, rgb,
                      dwords, depth);
 }
+template <int TASK>
+static void launch_views(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam, const LookRec& look,
+                         int W, int H, int ss, uint8_t* rgb, float* depth, hipStream_t st) {
+  if (!rgb) {
+    hipLaunchKernelGGL((k_views<TASK, false>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
+                       env_cam, look, W, H, ss, nullptr, 0, depth);
+    return;
+  }
+  // frame f starts at byte f * 3 W H of rgb: whole-dword stores need every frame's base to be a
+  // multiple of 4 bytes, so the frame size and the output base both have to be
+  const int dwords = (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;
+  hipLaunchKernelGGL((k_views<TASK, true>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
+                     env_cam, look, W, H, ss, rgb, dwords, depth);
+}
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
-                              launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>};
+                              launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();

@@ -162,10 +162,10 @@ struct RColors {
   unsigned bytes[4][48];             // one wave's 64 rgb pixels, repacked into dwords
 };
 
-// per-env colour table (tint rows: a colour channel read from the env's params) and light list
+// the part of the per-env colour table that no camera enters: entry colours (tint rows: a colour
+// channel read from the env's params) and the model's lights, behind the headlight's slot
 // (look: background rgb, headlight ambient / diffuse / specular, headlight on)
-AW_DEV void render_colors(const DModel& m, const Env& s, RColors& c, const float* cam, const float* look, int tid,
-                          int nthreads) {
+AW_DEV void render_colors_env(const DModel& m, const Env& s, RColors& c, const float* look, int tid, int nthreads) {
   const int ne = m.nrgeom + m.nrsite;
   for (int i = tid; i < ne * COL_W; i += nthreads) {
     const int e = i / COL_W, k = i - e * COL_W;
@@ -176,14 +176,44 @@ AW_DEV void render_colors(const DModel& m, const Env& s, RColors& c, const float
   }
   const int head = look[6] != 0.f ? 1 : 0;
   for (int i = tid; i < m.nlight * LIGHT_W; i += nthreads) c.light[head + i / LIGHT_W][i % LIGHT_W] = MD(light, i);
-  if (head && tid == 0) {   // the headlight: a point light at the camera, no cone, no attenuation
+  if (tid == 0) c.nlight = head + m.nlight;
+}
+
+// the headlight (light 0 when look switches it on): a point light at the camera, no cone, no
+// attenuation
+AW_DEV void render_headlight(RColors& c, const float* cam, const float* look, int tid) {
+  if (look[6] != 0.f && tid == 0) {
     float* q = c.light[0];
     for (int k = 0; k < LIGHT_W; k++) q[k] = 0.f;
     for (int k = 0; k < 3; k++) { q[k] = cam[k]; q[6 + k] = look[3]; q[9 + k] = look[4]; q[12 + k] = look[5]; }
     q[15] = 1.f;
     q[18] = -2.f;
   }
-  if (tid == 0) c.nlight = head + m.nlight;
+}
+
+// per-env colour table and light list of one camera
+AW_DEV void render_colors(const DModel& m, const Env& s, RColors& c, const float* cam, const float* look, int tid,
+                          int nthreads) {
+  render_colors_env(m, s, c, look, tid, nthreads);
+  render_headlight(c, cam, look, tid);
+}
+
+// world camera record of a view given in the frame of a body (s.xpos / s.xquat from
+// stage_kinematics): position xpos[b] + rot(xquat[b], pos), the three axes rotated by xquat[b],
+// the pixel map and zfar copied; body 0 (the world): the record as it is, no arithmetic
+AW_DEV void compose_view(const Env& s, const float* rec, int body, float* cam, int tid) {
+  if (tid < 4) {   // position, forward, up, right
+    float v[3], r[3];
+    copy3(v, rec + 3 * tid);
+    copy3(r, v);
+    if (body > 0) {
+      rotvq(r, v, s.xquat[body]);
+      if (tid == 0) add3(r, r, s.xpos[body]);
+    }
+    copy3(cam + 3 * tid, r);
+  } else if (tid < 9) {   // u0, du, v0, dv, zfar
+    cam[8 + tid] = rec[8 + tid];
+  }
 }
 
 // outward normal at the point lp of a primitive's surface (entry frame)

@@ -178,9 +178,49 @@ class AdroitVecEnv:
         self._cam, self._cam_key = free_camera(self.model, self.env_id, w, h, aerial=self._aerial), (w, h)
         return self._cam
 
-    def render_depth(self, width: int = 64, height: int = 64, out=None):
+    def _view(self, camera, width: int, height: int):
+        """(record, body) of one item of ``render_views``' camera list"""
+        from .render import model_camera
+        if isinstance(camera, str):
+            if camera == "free":
+                if getattr(self, "_cam_key", None) != (width, height):
+                    self.mj_viewer_headless_setup(width, height, aerial=getattr(self, "_aerial", False))
+                return self._cam, 0
+            return model_camera(self.model, camera, width, height)
+        rec, body = camera
+        return np.asarray(rec, np.float32), int(body)
+
+    def render_views(self, cameras, width: int = 64, height: int = 64, ss: int = 1, rgb: bool = True,
+                     depth: bool = False, env_cams=None, out=None, depth_out=None):
+        """Several cameras of every env's current state in one launch (``aw_render_views``).
+        ``cameras``: a list (at most 4) whose items are the name of one of the model's own cameras
+        (``"fixed"``, ``"vil_camera"``, pen's ``"view_1"`` ...), a ``(record, body)`` pair
+        (``render.mounted_camera``: a camera riding on a body, e.g. the palm; ``render.model_camera``)
+        or ``"free"``, the reference's free camera.  ``env_cams`` [N, V, 17] (device fp32, e.g.
+        ``render.jitter_cameras`` per view): per-env records used in place of the cameras' own, in
+        the frame of the same bodies.  Returns the colour frames [N, V, height, width, 3] (uint8),
+        the depth frames [N, V, height, width] (fp32, ``ss`` 1), or with both the pair."""
+        import torch
+        views = [self._view(c, width, height) for c in cameras]
+        n, nv = self.num_envs, len(views)
+        if rgb and out is None:
+            out = self.sim.empty(n, nv, height, width, 3, dtype=torch.uint8)
+        if depth and depth_out is None:
+            depth_out = self.sim.empty(n, nv, height, width)
+        self.sim.render_views(views, width, height, rgb=out if rgb else None, depth=depth_out if depth else None,
+                              env_cam=env_cams, ss=ss)
+        return (out, depth_out) if (rgb and depth) else (out if rgb else depth_out)
+
+    def render_depth(self, width: int = 64, height: int = 64, out=None, camera=None):
         """Depth frames [N, height, width] (metres, device) of every env's current state from
-        the reference's headless camera (headless_observer.py; mj_envs_amd/render.py)."""
+        the reference's headless camera (headless_observer.py; mj_envs_amd/render.py), or from
+        ``camera`` (an item of ``render_views``' list)."""
+        if camera is not None:
+            if out is None:
+                out = self.sim.empty(self.num_envs, height, width)
+            self.render_views([camera], width, height, rgb=False, depth=True,
+                              depth_out=out.view(self.num_envs, 1, height, width))
+            return out
         if getattr(self, "_cam_key", None) != (width, height):
             self.mj_viewer_headless_setup(width, height, aerial=getattr(self, "_aerial", False))
         if out is None:
@@ -188,12 +228,21 @@ class AdroitVecEnv:
         self.sim.render_depth(out, self._cam)
         return out
 
-    def render_rgb(self, width: int = 64, height: int = 64, ss: int = 1, out=None, depth_out=None):
+    def render_rgb(self, width: int = 64, height: int = 64, ss: int = 1, out=None, depth_out=None, camera=None):
         """Colour frames [N, height, width, 3] (uint8, device) of every env's current state from
         the same camera as ``render_depth`` (shading model: mj_envs_amd/render.py); ``ss`` 2
         averages 2x2 rays per pixel; ``depth_out`` [N, height, width] (fp32, ss 1) receives the
-        aligned depth frames of the same launch."""
+        aligned depth frames of the same launch.  ``camera``: an item of ``render_views``' list
+        instead of the free camera."""
         import torch
+        if camera is not None:
+            n = self.num_envs
+            if out is None:
+                out = self.sim.empty(n, height, width, 3, dtype=torch.uint8)
+            self.render_views([camera], width, height, ss=ss, rgb=True, depth=depth_out is not None,
+                              out=out.view(n, 1, height, width, 3),
+                              depth_out=None if depth_out is None else depth_out.view(n, 1, height, width))
+            return out
         if getattr(self, "_cam_key", None) != (width, height):
             self.mj_viewer_headless_setup(width, height, aerial=getattr(self, "_aerial", False))
         if out is None:
@@ -368,8 +417,10 @@ class _AdroitEnv(_reference_base()):
     def evaluate_success(self, paths: List[dict]) -> float:
         return _evaluate_success(self.env_id, paths)
 
-    def render(self, *args, mode: str = "depth", enable_resize: bool = True, **kwargs):
+    def render(self, *args, mode: str = "depth", enable_resize: bool = True, camera=None, **kwargs):
         """Default: the depth frame [height, width] (float64, metres) of the current state.
+        ``camera``: one of the model's own cameras by name, or a ``(record, body)`` pair
+        (``AdroitVecEnv.render_views``), instead of the reference's free camera.
         ``mode="rgb"``: the colour frame ``HeadlessObserver.render`` returns
         (headless_observer.py:34-52), float64 [H, W, 3] in 0..255 from the HIP ray caster's shading
         model (mj_envs_amd/render.py; parity-unpinned against the reference's OpenGL frame):
@@ -377,10 +428,10 @@ class _AdroitEnv(_reference_base()):
         else the 128x128 crop itself."""
         if mode == "rgb":
             size, ss = (64, 2) if enable_resize else (128, 1)
-            return self.vec.render_rgb(size, size, ss=ss)[0].cpu().numpy().astype(np.float64)
+            return self.vec.render_rgb(size, size, ss=ss, camera=camera)[0].cpu().numpy().astype(np.float64)
         if mode != "depth":
             raise ValueError(f"render: mode must be 'depth' or 'rgb', not {mode!r}")
-        return self.vec.render_depth(self.width, self.height)[0].cpu().numpy().astype(np.float64)
+        return self.vec.render_depth(self.width, self.height, camera=camera)[0].cpu().numpy().astype(np.float64)
 
     # pen's flag (pen_v0.py:23, read by its mj_viewer_headless_setup, :174-177)
     use_aerial_view = False

@@ -201,6 +201,9 @@ class Model:
         self.names: Dict[str, List[str]] = {}
         self.dims: Dict[str, int] = {}
         self.opt: Dict[str, float] = {}
+        # the model's <camera>s: names, cam_bodyid, cam_pos, cam_quat, cam_fovy.  Host side only --
+        # not in ``arrays``, so never in the device blob; None: no camera file was loaded
+        self.cameras: Optional[Dict[str, object]] = None
 
     def __getattr__(self, key):
         d = self.__dict__
@@ -250,6 +253,25 @@ class Model:
             payload.update({"o_" + k: np.array(v) for k, v in self.opt.items()})
         payload.update({"n_" + k: np.array(v, dtype="U64") for k, v in pick(self.names, APPEARANCE_NAMES).items()})
         np.savez_compressed(path, **payload)
+
+    def save_cameras(self, path: str):
+        """The camera table in a file of its own (settings and names only)."""
+        c = self.cameras
+        np.savez_compressed(path, names=np.array(c["names"], dtype="U64"), cam_bodyid=c["cam_bodyid"],
+                            cam_pos=c["cam_pos"], cam_quat=c["cam_quat"], cam_fovy=c["cam_fovy"])
+
+    def load_cameras(self, path: str):
+        with np.load(path, allow_pickle=False) as z:
+            self.cameras = dict(names=[str(s) for s in z["names"]], cam_bodyid=z["cam_bodyid"].astype(np.int32),
+                                cam_pos=z["cam_pos"], cam_quat=z["cam_quat"], cam_fovy=z["cam_fovy"])
+
+    def camera_id(self, name: str) -> int:
+        if self.cameras is None:
+            raise KeyError(f"camera {name!r}: this model was loaded without its camera table "
+                           "(tests/golden/cameras_*.npz, written by tools/compile_assets.py)")
+        if name not in self.cameras["names"]:
+            raise KeyError(f"camera {name!r}: the model declares {self.cameras['names']}")
+        return self.cameras["names"].index(name)
 
     @classmethod
     def load_npz(cls, path: str, into: Optional["Model"] = None) -> "Model":
@@ -312,6 +334,22 @@ class _Compiler:
         if "axisangle" in a:
             v = _floats(a["axisangle"])
             return axisangle2quat(v[:3], v[3])
+        if "xyaxes" in a:
+            # x as given, y orthogonalised against it, z = x cross y: the frame's columns
+            v = np.array(_floats(a["xyaxes"]))
+            x = v[:3] / np.linalg.norm(v[:3])
+            y = v[3:] - x * (x @ v[3:])
+            y = y / np.linalg.norm(y)
+            return mat2quat(np.stack([x, y, np.cross(x, y)], axis=1))
+        if "zaxis" in a:
+            # the minimal rotation that takes +z to the given axis
+            z = np.array(_floats(a["zaxis"]))
+            z = z / np.linalg.norm(z)
+            axis = np.cross([0.0, 0.0, 1.0], z)
+            s = np.linalg.norm(axis)
+            if s < MJ_MINVAL:
+                return np.array([1.0, 0, 0, 0]) if z[2] > 0 else np.array([0.0, 1.0, 0, 0])
+            return axisangle2quat(axis / s, np.arctan2(s, z[2]))
         return np.array([1.0, 0, 0, 0])
 
     # --- tree walk ------------------------------------------------------------------
@@ -347,8 +385,13 @@ class _Compiler:
                     raise NotImplementedError("lights outside the worldbody are not used by the Adroit models")
                 self.lights.append(dict(child.attrib))
             elif tag == "camera":
-                # position only: the render camera needs cam_xpos (headless_observer.py:59-66)
-                body["cameras"].append(np.array(_floats(child.get("pos", "0 0 0"))))
+                # the free camera needs cam_xpos (headless_observer.py:59-66); the model's own
+                # cameras are rendered from their pose and fovy (render.model_camera)
+                a = child.attrib
+                if a.get("mode", "fixed") != "fixed":
+                    raise NotImplementedError(f"camera mode {a['mode']!r}: only fixed cameras are rendered")
+                body["cameras"].append(dict(name=a.get("name", ""), pos=np.array(_floats(a.get("pos", "0 0 0"))),
+                                            quat=self._orient(a), fovy=float(a.get("fovy", "45"))))
             elif tag == "body":
                 children.append(child)
         for child in children:
@@ -734,7 +777,12 @@ class _Compiler:
         A["light_exponent"] = np.array([float(a.get("exponent", "10")) for a in self.lights])
         cams = [(bi, c) for bi, b in enumerate(B) for c in b.get("cameras", [])]
         A["cam_bodyid"] = np.array([bi for bi, _ in cams], np.int32)
-        A["cam_pos"] = np.array([c for _, c in cams], np.float64).reshape(len(cams), 3)
+        A["cam_pos"] = np.array([c["pos"] for _, c in cams], np.float64).reshape(len(cams), 3)
+        # the camera table: host side only (never part of the device blob; Model.save_cameras)
+        m.cameras = dict(names=[c["name"] for _, c in cams], cam_bodyid=A["cam_bodyid"].copy(),
+                         cam_pos=A["cam_pos"].copy(),
+                         cam_quat=np.array([c["quat"] for _, c in cams], np.float64).reshape(len(cams), 4),
+                         cam_fovy=np.array([c["fovy"] for _, c in cams], np.float64))
         A["tendon_adr"] = np.array(ten_adr, np.int32)
         A["tendon_num"] = np.array(ten_num, np.int32)
         A["tendon_limited"] = np.array(ten_limited, np.int32)

@@ -42,6 +42,14 @@ head's red channel to ``mass / 2.5`` as the reference does (``hammer_v0.py:118``
 this is parity-unpinned against the reference's OpenGL frame; it is checked against an fp64 numpy
 restatement of the model above (``tests/rgb_checker.py``, ``tests/test_render_rgb.py``).
 
+Other cameras (``aw_render_views``, ``k_views``): a record may be given in the frame of a body
+(0: the world) and the kernel composes the world record from that body's pose, so the models'
+own ``<camera>``s (``model_camera``: ``fixed``, ``vil_camera``, pen's ``view_1..5``), a camera
+riding on a body (``mounted_camera``: an eye-in-hand view on the palm) and one record per env
+(``jitter_cameras``: pose and field-of-view randomisation) render through the same ray caster, up
+to four views of every env per launch.  ``free_camera`` and the two single-camera entry points
+are unchanged.
+
 Reference quirks kept: hammer sets up its observer once, in ``__init__``, while ``obj_bid`` is
 still the placeholder ``-1`` (``hammer_v0.py:15,35-38``), so the elevation uses the LAST body.
 door and relocate construct their observer with placeholder body 0 (``door_v0.py:16,41``,
@@ -123,3 +131,90 @@ def pixel_rays(cam: np.ndarray, width: int, height: int) -> np.ndarray:
     v = cam[14] - cam[15] * np.arange(height)
     d = fwd[None, None] + u[None, :, None] * right[None, None] + v[:, None, None] * up[None, None]
     return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+# ---------------------------------------------------------------------------------------
+# cameras in the frame of a body (aw_render_views): a record keeps the layout above, expressed in
+# the frame of a body (0: the world); the kernel composes the world record from the body's pose
+def pinhole_record(pos, R, width: int, height: int, fovy: float, zfar: float = ZFAR) -> np.ndarray:
+    """The record of a MuJoCo fixed camera at ``pos`` with frame ``R`` (3x3, columns x / y / z):
+    it looks along -z, up is +y, right is +x; vertical field of view ``fovy`` degrees over the
+    full ``width`` x ``height`` frame (no crop), rays through the pixel centres."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    ty = math.tan(math.radians(float(fovy)) / 2.0)
+    tx = ty * width / height
+    rec = np.concatenate([np.asarray(pos, np.float64), -R[:, 2], R[:, 1], R[:, 0],
+                          [-tx + tx / width, 2.0 * tx / width, ty - ty / height, 2.0 * ty / height, zfar]])
+    assert rec.size == CAM_FLOATS
+    return rec.astype(np.float32)
+
+
+def model_camera(model, name: str, width: int = 64, height: int = 64, zfar: float = ZFAR):
+    """``(record, body)`` of the model's own camera ``name`` (``fixed``, ``vil_camera``, pen's
+    ``view_1`` ...) from the camera table of ``tasks.load_model``; ``KeyError`` if the model was
+    loaded without it or declares no such camera."""
+    i = model.camera_id(name)
+    c = model.cameras
+    return (pinhole_record(c["cam_pos"][i], quat2mat(c["cam_quat"][i]), width, height, c["cam_fovy"][i], zfar),
+            int(c["cam_bodyid"][i]))
+
+
+def mounted_camera(model, body, pos, forward, up, width: int = 64, height: int = 64, fovy: float = FOVY_DEG,
+                   zfar: float = ZFAR):
+    """``(record, body id)`` of a user camera riding on ``body`` (a name or an id; 0 / "world": a
+    static camera): ``pos``, ``forward`` and ``up`` in the body's frame, ``up`` orthogonalised
+    against ``forward``.  An eye-in-hand view is a camera on ``palm``."""
+    bid = model.name2id("body", body) if isinstance(body, str) else int(body)
+    if not 0 <= bid < model.nbody:
+        raise ValueError(f"mounted_camera: body {body!r} is not a body of the model")
+    f = np.asarray(forward, np.float64)
+    f = f / np.linalg.norm(f)
+    u = np.asarray(up, np.float64)
+    u = u - f * (f @ u)
+    if np.linalg.norm(u) < 1e-9:
+        raise ValueError("mounted_camera: up is parallel to forward")
+    u = u / np.linalg.norm(u)
+    return pinhole_record(pos, np.stack([np.cross(f, u), u, -f], axis=1), width, height, fovy, zfar), bid
+
+
+def jitter_cameras(record, n: int, rng: np.random.Generator, pos_sigma: float = 0.0, rot_sigma_deg: float = 0.0,
+                   fovy_scale_range=(1.0, 1.0)) -> np.ndarray:
+    """``[n, 17]`` float32 per-env records around ``record`` (camera randomisation; the ``env_cam``
+    rows of one view): per env a rotation by N(0, ``rot_sigma_deg``) degrees about a uniformly
+    random axis applied to forward / up / right (Rodrigues, then re-orthonormalised: forward kept,
+    up made orthogonal to it, right = forward x up), a N(0, ``pos_sigma``) offset of the position on
+    each axis, and one factor drawn uniformly from ``fovy_scale_range`` on ``u0, du, v0, dv`` (the
+    tangent of the half field of view).  Zero sigmas and a unit range return ``record`` n times."""
+    rec = np.asarray(record, np.float64).reshape(CAM_FLOATS)
+    out = np.tile(rec, (n, 1))
+    lo, hi = fovy_scale_range
+    for e in range(n):
+        axis = rng.normal(size=3)
+        ang = math.radians(rot_sigma_deg) * rng.normal()
+        dp = pos_sigma * rng.normal(size=3)
+        sc = rng.uniform(lo, hi)
+        if pos_sigma != 0.0:
+            out[e, 0:3] = rec[0:3] + dp
+        if rot_sigma_deg != 0.0:
+            k = axis / np.linalg.norm(axis)
+            rot = lambda v: v * math.cos(ang) + np.cross(k, v) * math.sin(ang) + k * (k @ v) * (1.0 - math.cos(ang))
+            f = rot(rec[3:6])
+            f = f / np.linalg.norm(f)
+            u = rot(rec[6:9])
+            u = u - f * (f @ u)
+            u = u / np.linalg.norm(u)
+            out[e, 3:6], out[e, 6:9], out[e, 9:12] = f, u, np.cross(f, u)
+        if (lo, hi) != (1.0, 1.0):
+            out[e, 12:16] = rec[12:16] * sc
+    return out.astype(np.float32)
+
+
+def compose_record(record, xpos, xquat) -> np.ndarray:
+    """The world record (fp64) of ``record`` given in the frame of a body at ``xpos`` / ``xquat``:
+    what the kernel computes in fp32 (host-side helper for checks)."""
+    rec = np.asarray(record, np.float64).copy()
+    R = quat2mat(np.asarray(xquat, np.float64))
+    rec[0:3] = np.asarray(xpos, np.float64) + R @ rec[0:3]
+    for k in (3, 6, 9):
+        rec[k:k + 3] = R @ rec[k:k + 3]
+    return rec

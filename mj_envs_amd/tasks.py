@@ -62,10 +62,18 @@ def appearance_path(xml: str) -> str:
     return os.path.join(APPEARANCE_DIR, "appearance_" + xml.replace(".xml", ".npz"))
 
 
+def cameras_path(xml: str) -> str:
+    """the model's camera table (names, bodies, poses, fovy of its <camera>s), next to its appearance"""
+    return os.path.join(APPEARANCE_DIR, "cameras_" + xml.replace(".xml", ".npz"))
+
+
 def load_model(env_id: str):
     """Compiled model for ``env_id`` (committed ``models/*.npz`` plus its appearance part,
-    ``tests/golden/appearance_*.npz``; both built by tools/compile_assets.py).  Without the
-    appearance file the model still simulates and renders depth; only colour is unavailable."""
+    ``tests/golden/appearance_*.npz``, and its camera table, ``tests/golden/cameras_*.npz``; all
+    built by tools/compile_assets.py).  Without the appearance file the model still simulates and
+    renders depth; only colour is unavailable.  The camera table stays on the host
+    (``model.cameras``, never in ``model.arrays`` or the device blob); without its file only the
+    lookup of a model camera by name fails (``KeyError``)."""
     from .mjcf import Model
     spec = TASKS[env_id]
     path = os.path.join(MODEL_DIR, spec.xml.replace(".xml", ".npz"))
@@ -74,6 +82,8 @@ def load_model(env_id: str):
     m = Model.load_npz(path)
     if os.path.exists(appearance_path(spec.xml)):
         Model.load_npz(appearance_path(spec.xml), into=m)
+    if os.path.exists(cameras_path(spec.xml)):
+        m.load_cameras(cameras_path(spec.xml))
     return m
 
 

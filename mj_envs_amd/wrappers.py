@@ -66,6 +66,15 @@ class PixelObservationVecEnv:
         self.mode, self.ss = rk.get("mode", "depth"), int(rk.get("ss", 1))
         if self.mode not in ("depth", "rgb"):
             raise ValueError(f"render_kwargs['mode'] must be 'depth' or 'rgb', not {self.mode!r}")
+        # render_kwargs["camera"]: a model camera's name, a (record, body) pair or "free" -- or a list
+        # of those, rendered in one launch as [N, V, ...]; render_kwargs["env_cams"]: per-env records
+        # [N, V, 17] (AdroitVecEnv.render_views).  Without the key: the reference's free camera.
+        cam = rk.get("camera")
+        self.cameras = None if cam is None else (list(cam) if isinstance(cam, list) else [cam])
+        self.multi_view = isinstance(cam, list)
+        self.env_cams = rk.get("env_cams")
+        if self.env_cams is not None and self.cameras is None:
+            raise ValueError("render_kwargs['env_cams'] needs render_kwargs['camera']")
         self.action_repeat = int(action_repeat)
         self.max_episode_length = 200          # wrappers.py:39 (hard-coded there too)
         import torch
@@ -76,6 +85,10 @@ class PixelObservationVecEnv:
         self.state_space = env.observation_space
         self.pixel_space = Box(0.0, 255.0, (self.height, self.width, 3)) if self.mode == "rgb" \
             else Box(0.0, np.inf, (1, self.height, self.width))
+        if self.multi_view:
+            nv = len(self.cameras)
+            self.pixel_space = Box(0.0, 255.0, (nv, self.height, self.width, 3)) if self.mode == "rgb" \
+                else Box(0.0, np.inf, (nv, self.height, self.width))
         self.observation_space = self.pixel_space if obs_key == PIXELS_KEY else self.state_space
 
     # --- observations --------------------------------------------------------------------
@@ -88,7 +101,9 @@ class PixelObservationVecEnv:
     def get_pixels(self):
         if not self._pixels_fresh:
             n, h, w = self.num_envs, self.height, self.width
-            if self.mode == "rgb":
+            if self.cameras is not None:
+                self._render_cameras(n, h, w)
+            elif self.mode == "rgb":
                 if self._pixels is None:
                     import torch
                     self._rgb8 = self.env.sim.empty(n, h, w, 3, dtype=torch.uint8)   # what the kernel writes
@@ -101,6 +116,23 @@ class PixelObservationVecEnv:
                 self.env.render_depth(w, h, out=self._pixels.view(n, h, w))
             self._pixels_fresh = True
         return self._out(self._pixels)
+
+    def _render_cameras(self, n, h, w):
+        """the pixels of render_kwargs["camera"]: one launch for all its views; a single camera
+        keeps the shapes of the free camera's observation"""
+        nv = len(self.cameras)
+        if self.mode == "rgb":
+            if self._pixels is None:
+                import torch
+                self._rgb8 = self.env.sim.empty(n, nv, h, w, 3, dtype=torch.uint8)
+                self._pixels = self.env.sim.empty(n, nv, h, w, 3) if self.multi_view else self.env.sim.empty(n, h, w, 3)
+            self.env.render_views(self.cameras, w, h, ss=self.ss, env_cams=self.env_cams, out=self._rgb8)
+            self._pixels.view(n, nv, h, w, 3).copy_(self._rgb8)                      # float32 0..255
+        else:
+            if self._pixels is None:
+                self._pixels = self.env.sim.empty(n, nv, h, w)     # one camera: [N, 1, H, W] as before
+            self.env.render_views(self.cameras, w, h, rgb=False, depth=True, env_cams=self.env_cams,
+                                  depth_out=self._pixels)
 
     def _obs(self):
         return self.get_pixels() if self.obs_key == PIXELS_KEY else self.get_state()
@@ -235,7 +267,9 @@ def make_env(config, num_envs: int = 1, device: int = 0):
     ``config.variation_type``, ``config.state_type`` ('observation' -> pixels, 'vector' ->
     state), ``config.nogui`` (False: the GUI wrapper, state tensors, no pixels); optional
     ``config.pixel_mode``: ``"depth"`` (default) or ``"rgb"`` (colour pixels, 2x2 rays per pixel:
-    the reference's resized frame); optional ``config.sensors``: MuJoCo's sensordata in
+    the reference's resized frame); optional ``config.camera``: the pixels' camera -- a model
+    camera's name, a ``(record, body)`` pair or a list of those (``render_kwargs["camera"]``;
+    default: the reference's free camera); optional ``config.sensors``: MuJoCo's sensordata in
     ``info["sensordata"]`` of every step (``AdroitVecEnv(sensors=True)``); optional ``config.data``
     (True or group names) and ``config.max_contacts``: the batched ``sim.data`` views in ``env.data``
     (``AdroitVecEnv(data=...)``)."""
@@ -251,6 +285,8 @@ def make_env(config, num_envs: int = 1, device: int = 0):
         rk.update(mode="rgb", ss=2)
     elif mode != "depth":
         raise Exception(f"Unsupported pixel mode '{mode}'")
+    if getattr(config, "camera", None) is not None:
+        rk.update(camera=config.camera)
     if not getattr(config, "nogui", True):
         return PixelObservationVecEnv(env, obs_key=STATE_KEY, render_kwargs=rk)
     st = getattr(config, "state_type", "vector")
