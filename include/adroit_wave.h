@@ -307,6 +307,33 @@ typedef struct { float rec[AW_CAM_FLOATS]; int32_t body; } aw_view;
 int aw_render_views(aw_handle* h, const aw_view* views, int nviews, const float* env_cam, const float* look,
                     int width, int height, int ss, uint8_t* rgb, float* depth, void* stream);
 
+/* Segmentation frames: what each pixel of a camera shows (mujoco-py's sim.render(...,
+ * segmentation=True)).  The ray caster's render entries are the primitive (non-mesh) geoms in model
+ * order, then the visible sites (group 0-2, alpha > 0) in site order; aw_render_entries returns the
+ * two counts (nsite is 0 on a table without the appearance arrays).
+ *   aw_render_labels renders the views of aw_render_views (views, nviews, env_cam as there; env_cam
+ * is always [N][nviews][AW_CAM_FLOATS], indexed by env id) into labels [n][nviews][height][width]
+ * int32: per pixel lut[entry] of the nearest geom crossing (the depth renderer's search), or
+ * background where the ray hits nothing.  Geoms that cross within 2e-3 m of the nearest (links
+ * that overlap at a joint, coplanar faces) are ordered by a crossing re-evaluated from an origin
+ * next to the geom, good to about 1e-6 m; what that cannot tell apart goes to the lower entry.
+ * sites 1: the nearest visible site crossing strictly in
+ * front of that geom replaces it (a geom wins a tie; among sites the nearest, then the lower entry):
+ * sites are drawn solid, as MuJoCo's segmentation draws them.  sites 0 needs no appearance arrays.
+ *   lut: HOST array of ngeom + nsite labels or NULL (the entry index itself); mj_envs_amd/labels.py
+ * builds tables of model geom ids, body ids, body classes and mujoco-py's objtype << 16 | objid.
+ *   env_ids: NULL (every env, n = N, n_sel ignored) or DEVICE array of n_sel env ids: output row k
+ * is env env_ids[k] (n = n_sel).  An id outside [0, N) leaves its row untouched.
+ *   depth: NULL or DEVICE [n][nviews][height][width], bit for bit the depth frames of
+ * aw_render_views depth-only (sites never write depth).
+ * AW_EINVAL: nviews outside 1..AW_MAX_VIEWS, a body outside [0, nbody), NULL labels, sizes <= 0 or
+ * > 1024, n_sel < 1 with env_ids given, sites not 0 or 1.  AW_EUNSUPPORTED: sites 1 on a model
+ * table without the appearance arrays. */
+int aw_render_entries(const aw_handle* h, int* ngeom, int* nsite);
+int aw_render_labels(aw_handle* h, const aw_view* views, int nviews, const float* env_cam,
+                     const int32_t* env_ids, int n_sel, const int32_t* lut, int32_t background,
+                     int sites, int width, int height, int32_t* labels, float* depth, void* stream);
+
 /* On-device Gaussian MLP policy: mjrl gaussian_mlp.MLP as used by the
  * reference's DAPG baseline (algos/baselines.py:67-86, hidden_sizes=(32, 32)) -- two tanh
  * hidden layers of width `hidden` (32 or 64), in/out affine transforms, and with sample != 0

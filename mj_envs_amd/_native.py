@@ -161,6 +161,12 @@ def load():
         L.aw_render_views.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, _vp, _vp, _vp]
         L.aw_render_views.restype = ctypes.c_int
+    if hasattr(L, "aw_render_labels"):
+        L.aw_render_entries.argtypes = [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        L.aw_render_entries.restype = ctypes.c_int
+        L.aw_render_labels.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
+                                       ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]
+        L.aw_render_labels.restype = ctypes.c_int
     if hasattr(L, "aw_policy_mlp"):
         L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, _vp]
@@ -180,7 +186,7 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
            "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_render_rgb",
-           "aw_render_views", "aw_policy_mlp",
+           "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_policy_mlp",
            "aw_collide_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
@@ -464,6 +470,54 @@ class Sim:
             assert lk.size == 7, "render_views: look record has 7 floats"
         _check(load().aw_render_views(self.h, arr, nv, _ptr(env_cam), None if lk is None else lk.ctypes.data, w, h,
                                       int(ss), _ptr(rgb), _ptr(depth), _stream()))
+
+    def render_entries(self):
+        """(ngeom, nsite) of the ray caster's render entries: the primitive geoms in model order, then
+        the visible sites in site order (include/adroit_wave.h aw_render_entries)"""
+        ng, ns = ctypes.c_int(0), ctypes.c_int(0)
+        _check(load().aw_render_entries(self.h, ctypes.byref(ng), ctypes.byref(ns)))
+        return ng.value, ns.value
+
+    def render_labels(self, views, width: int, height: int, labels, depth=None, env_cam=None, env_ids=None,
+                      lut=None, background: int = -1, sites=0, n_sel: Optional[int] = None):
+        """Segmentation frames of every view in one launch (include/adroit_wave.h aw_render_labels).
+        views, env_cam: as in render_views (env_cam is [n_envs, V, 17] whatever env_ids selects);
+        env_ids [n] (device, int32): output row k shows env env_ids[k] (None: every env, n = n_envs);
+        labels [n, V, H, W] (device, int32) and optionally depth [n, V, H, W] (device, fp32);
+        lut: host ints, one label per render entry (None: the entry index); background: the label
+        of a pixel that shows nothing; sites 1: the visible sites are drawn too.  n_sel: the count
+        handed to the library with env_ids (default: their number)."""
+        import torch
+        nv = len(views)
+        w, h = int(width), int(height)
+        arr = (View * max(nv, 1))()
+        for k, (rec, body) in enumerate(views):
+            c = np.ascontiguousarray(rec, np.float32)
+            assert c.size == 17, "render_labels: a camera record has 17 floats"
+            arr[k].rec[:] = c.ravel().tolist()
+            arr[k].body = int(body)
+        n = self.n_envs
+        if env_ids is not None:
+            assert env_ids.dim() == 1 and env_ids.dtype == torch.int32 and env_ids.is_contiguous() and \
+                env_ids.is_cuda, "render_labels: env_ids must be a device int32 vector"
+            n = int(env_ids.shape[0])
+        if labels is not None:
+            assert tuple(labels.shape) == (n, nv, h, w) and labels.dtype == torch.int32 and labels.is_contiguous(), \
+                "render_labels: labels must be int32 [n, V, H, W]"
+        if depth is not None:
+            assert tuple(depth.shape) == (n, nv, h, w) and depth.dtype == torch.float32 and depth.is_contiguous(), \
+                "render_labels: depth must be fp32 [n, V, H, W]"
+        if env_cam is not None:
+            assert tuple(env_cam.shape) == (self.n_envs, nv, 17) and env_cam.dtype == torch.float32 and \
+                env_cam.is_contiguous(), "render_labels: env_cam must be fp32 [n_envs, V, 17]"
+        lt = None
+        if lut is not None:
+            lt = np.ascontiguousarray(lut, np.int32)
+            assert lt.ndim == 1 and lt.size == sum(self.render_entries()), \
+                "render_labels: lut has one label per render entry"
+        _check(load().aw_render_labels(self.h, arr, nv, _ptr(env_cam), _ptr(env_ids), n if n_sel is None else int(n_sel),
+                                       None if lt is None else lt.ctypes.data, int(background), int(sites), w, h,
+                                       _ptr(labels), _ptr(depth), _stream()))
 
     def collide_test(self, types, pos, mat, size, margin, fp64: bool = False):
         """narrowphase of n primitive pairs (test hook): list of arrays [(dist, pos[3], normal[3]), ...]

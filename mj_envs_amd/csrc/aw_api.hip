@@ -614,6 +614,39 @@ int aw_render_views(aw_handle* h, const aw_view* views, int nviews, const float*
   return AW_OK;
 }
 
+int aw_render_entries(const aw_handle* h, int* ngeom, int* nsite) {
+  if (!h || !ngeom || !nsite) return fail(AW_EINVAL, "aw_render_entries: null");
+  *ngeom = h->m.nrgeom;
+  *nsite = h->m.nrsite;
+  return AW_OK;
+}
+
+int aw_render_labels(aw_handle* h, const aw_view* views, int nviews, const float* env_cam, const int32_t* env_ids,
+                     int n_sel, const int32_t* lut, int32_t background, int sites, int width, int height,
+                     int32_t* labels, float* depth, void* stream) {
+  if (!h || !views || nviews < 1 || nviews > AW_MAX_VIEWS || !labels || width <= 0 || height <= 0 || width > 1024 ||
+      height > 1024 || (env_ids && n_sel < 1) || (sites != 0 && sites != 1))
+    return fail(AW_EINVAL, "aw_render_labels: bad arguments");
+  for (int v = 0; v < nviews; v++)
+    if (views[v].body < 0 || views[v].body >= h->m.nbody)
+      return fail(AW_EINVAL, "aw_render_labels: a view's body is not a body of the model");
+  if (sites && !h->m.appearance)
+    return fail(AW_EUNSUPPORTED, "aw_render_labels: the model table carries no appearance arrays (no visible sites)");
+  HIPCHK(hipSetDevice(h->device));
+  ViewsRec r = {};
+  for (int v = 0; v < nviews; v++) {
+    memcpy(r.c[v], views[v].rec, sizeof(r.c[v]));   // host array: the records travel as a kernel argument
+    r.body[v] = views[v].body;
+  }
+  const int ne = h->m.nrgeom + h->m.nrsite;
+  LutRec l;
+  for (int e = 0; e < MAXRG; e++) l.v[e] = e < ne && lut ? lut[e] : e;   // and so does the table
+  h->ops->labels(h, r, nviews, env_cam, env_ids, env_ids ? n_sel : h->nenv, l, background, sites, width, height, labels,
+                 depth, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
 int aw_policy_mlp(int n, int in_dim, int hidden, int out_dim, const float* params, const float* obs, float* act,
                   int sample, uint64_t seed, uint64_t step, uint64_t env_offset, void* stream) {
   if (n <= 0 || !params || !obs || !act || in_dim <= 0 || in_dim > MLP_IMAX || out_dim <= 0 || out_dim > MLP_OMAX)

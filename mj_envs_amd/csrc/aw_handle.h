@@ -24,7 +24,7 @@ struct DState {
   int* n_success;         // finished episodes with > success_steps goal steps (evaluate_success)
 };
 
-// the camera and look records of the render kernels (k_depth, k_rgb, k_views): host arrays that travel as
+// the camera and look records of the render kernels (k_depth, k_rgb, k_views, k_labels): host arrays that travel as
 // kernel arguments
 struct CamRec {
   float c[AW_CAM_FLOATS];
@@ -36,6 +36,10 @@ struct LookRec {
 struct ViewsRec {
   float c[AW_MAX_VIEWS][AW_CAM_FLOATS];
   int body[AW_MAX_VIEWS];
+};
+// the look-up table of one aw_render_labels launch (k_labels): render entry -> label
+struct LutRec {
+  int v[MAXRG];
 };
 
 struct TaskOps;
@@ -109,6 +113,8 @@ struct TaskOps {
   void (*rgb)(aw_handle*, const CamRec&, const LookRec&, int, int, int, uint8_t*, float*, hipStream_t);
   void (*views)(aw_handle*, const ViewsRec&, int, const float*, const LookRec&, int, int, int, uint8_t*, float*,
                 hipStream_t);
+  void (*labels)(aw_handle*, const ViewsRec&, int, const float*, const int32_t*, int, const LutRec&, int32_t, int, int,
+                 int, int32_t*, float*, hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 

@@ -1,7 +1,7 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
 // -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_dump, k_depth, k_rgb, k_views,
-// k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
+// k_labels, k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
 // k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
 // env-step both tiers run is aw_step.h.
 #ifndef AW_TASK_TU
@@ -397,6 +397,56 @@ __global__ void __launch_bounds__(256) k_views(DModel m, DState st, int n, Views
   }
 }
 
+// segmentation frames (aw_render_labels): k_views<TASK, false>'s structure -- the staging and the
+// kinematics once per env, per view compose_view, the pixel boxes and the 64-pixel spans -- writing
+// one int32 label per pixel (aw_render.h render_span_labels) and optionally the depth frame.
+// SITES: the visible sites join the entries.  The workgroup renders env env_ids[blockIdx.x] (NULL:
+// blockIdx.x) into output row blockIdx.x; an id outside [0, n) is uniform over the block, which
+// leaves before its first barrier with its row untouched.  The env id selects what is read (the
+// state, the params, env_cam's records); every output index is blockIdx.x, the view and the lane.
+// The look-up table travels as a kernel argument and is staged into LDS once.
+template <int TASK, bool SITES>
+__global__ void __launch_bounds__(256) k_labels(DModel m, DState st, int n, ViewsRec views, int nviews,
+                                                const float* __restrict__ env_cam, const int* __restrict__ env_ids,
+                                                LutRec lut, int background, int W, int H, int* labels, float* depth) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RGeoms rg;
+  __shared__ float lcam[AW_CAM_FLOATS];
+  __shared__ int slut[MAXRG];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
+  if (env < 0 || env >= n) return;
+  if (tid < 64) {
+    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+    wsync();
+    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+    stage_kinematics(m, s, lane);
+  } else if (tid < 64 + MAXRG) {
+    slut[tid - 64] = lut.v[tid - 64];
+  }
+  __syncthreads();
+  const int ns = SITES ? m.nrsite : 0;
+  const size_t np = (size_t)W * H;
+  for (int v = 0; v < nviews; v++) {
+    const size_t frame = (size_t)blockIdx.x * nviews + v;
+    compose_view(s, env_cam ? env_cam + ((size_t)env * nviews + v) * AW_CAM_FLOATS : views.c[v], views.body[v], lcam,
+                 tid);
+    __syncthreads();
+    // the record is uniform over the block: held in scalar registers, as in k_views
+    float cam[AW_CAM_FLOATS];
+    for (int k = 0; k < AW_CAM_FLOATS; k++)
+      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    render_geoms(m, s, rg, cam, tid, 256);
+    if constexpr (SITES) render_sites(m, s, rg, cam, tid, 256);
+    __syncthreads();
+    float* z = depth ? depth + frame * np : nullptr;
+    for (int p0 = (tid >> 6) * 64; p0 < W * H; p0 += 256)
+      render_span_labels(rg, m.nrgeom, ns, cam, slut, background, W, H, p0, lane, labels + frame * np, z);
+    __syncthreads();   // the next view overwrites cam and the boxes
+  }
+}
+
 // Claim order for the next k_step launch (longest processing time first): per XCD class c (k_step's
 // env range [n c / 8, n (c + 1) / 8)) the envs are bucketed by their last env-step's shader cycles
 // on a quarter-octave scale and written costliest bucket first into perm (positions of the same
@@ -494,10 +544,23 @@ static void launch_views(aw_handle* h, const ViewsRec& views, int nviews, const 
   hipLaunchKernelGGL((k_views<TASK, true>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
                      env_cam, look, W, H, ss, rgb, dwords, depth);
 }
+// grid: the output rows (the selected envs, or all of them)
+template <int TASK>
+static void launch_labels(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam, const int32_t* env_ids,
+                          int grid, const LutRec& lut, int32_t background, int sites, int W, int H, int32_t* labels,
+                          float* depth, hipStream_t st) {
+  if (sites)
+    hipLaunchKernelGGL((k_labels<TASK, true>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
+                       env_cam, env_ids, lut, background, W, H, labels, depth);
+  else
+    hipLaunchKernelGGL((k_labels<TASK, false>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
+                       env_cam, env_ids, lut, background, W, H, labels, depth);
+}
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
-                              launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>};
+                              launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
+                              launch_labels<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();

@@ -1,9 +1,9 @@
-// aw_render.h -- depth and colour ray casting against primitive geoms and sites (fp32).
+// aw_render.h -- depth, colour and segmentation ray casting against primitive geoms and sites (fp32).
 //
 // Replaces the reference's OpenGL frame (hand_manipulation_suite/headless_observer.py:34-52)
 // with metric z-depth and a Phong-shaded colour frame; see mj_envs_amd/render.py for the camera
 // construction and the shading model.  numpy restatements for the tests: oracle/depth.py
-// (geometry), tests/rgb_checker.py (colour).
+// (geometry), tests/rgb_checker.py (colour), tests/label_checker.py (segmentation).
 #pragma once
 #include "aw_common.h"
 #include "aw_dynamics.h"
@@ -151,9 +151,98 @@ AW_DEV void render_span(const RGeoms& r, int ng, const float* cam, int W, int H,
   if (p < np) out[p] = best < 1.0e38f ? best * dot3(d, cam + 3) : cam[16];
 }
 
+// Segmentation.  nearest_hit's crossings carry the cancellation of ray_geom's quadratic, b^2 - a c
+// with the ray origin metres from a round geom a few millimetres thick: about 1e-4 m for a finger
+// link 4.5 m from the free camera.  Depth takes that (2e-3 m is its gate), a label does not: where
+// two links overlap at a joint, crossings 3e-4 m apart change their order and the pixel names a
+// link that no ray near it sees.  So labels order the entries that cross within LABEL_TIE of the
+// nearest by entry_near: the crossing from an origin moved along the ray to two bounding radii in
+// front of the entry's centre, where the same fp32 arithmetic is good to about 1e-6 m.
+// Crossings that entry_near cannot tell apart (LABEL_EPS of the distance: coplanar faces, such as a
+// cylinder's cap flush with a box) go to the lower entry, as an exact tie does.
+constexpr float LABEL_TIE = 2.0e-3f;   // the depth gate: what nearest_hit's order is trusted to
+constexpr float LABEL_EPS = 4.0e-6f;   // of t: a few times entry_near's error (ulp(t) for the moved origin and the sum)
+
+// entry_hit's culls against lim, then the crossing t of entry g along cam + t d evaluated from the
+// origin cam + s d, s = max(0, (centre - cam) . d - 2 rbound) (outside the bounding sphere, in front
+// of it; planes, rbound 0: from cam itself, no quadratic), or -1
+AW_DEV float entry_near(const RGeoms& r, int g, const float* cam, const float* d, float fc, float fr, float lim) {
+  if (fc < r.box[g][0] || fc > r.box[g][1] || fr < r.box[g][2] || fr > r.box[g][3]) return -1.f;
+  const float rb = r.rb[g];
+  float s = 0.f;
+  if (rb > 0.f) {
+    float oc[3];
+    sub3(oc, r.pos[g], cam);
+    const float tc = dot3(oc, d);
+    const float d2 = dot3(oc, oc) - tc * tc;
+    if (d2 > rb * rb || tc + rb < 0.f || tc - rb > lim) return -1.f;
+    s = fmaxf(tc - 2.f * rb, 0.f);
+  }
+  float o[3];
+  for (int k = 0; k < 3; k++) o[k] = cam[k] + s * d[k];
+  const float t = ray_prim(r.pos[g], r.mat[g], r.size[g], r.type[g], o, d);
+  return t >= 0.f ? s + t : -1.f;
+}
+
+// segmentation label (and optionally z-depth) of the 64 pixels [p0, p0 + 64) handled by one wave.
+// Geoms: render_span's search (nearest_hit's loop) says whether the ray hits anything and how deep -- depth
+// is written from it, so it is render_span's depth bit for bit, and a pixel is background exactly
+// where that depth is zfar; among the geoms crossing within LABEL_TIE of it the nearest by
+// entry_near is the label (within LABEL_EPS the lower entry).  Sites (ns > 0): the nearest
+// visible-site crossing in front of that geom replaces it (a geom wins a tie; among sites the
+// nearest, then the lower entry -- "in front of the opaque crossing" as render_span_rgb blends, drawn
+// solid), by entry_near as well.  One dword per lane: lut[entry], or background.
+AW_DEV void render_span_labels(const RGeoms& r, int ng, int ns, const float* cam, const int* lut, int background,
+                               int W, int H, int p0, int lane, int* out, float* depth) {
+  const int np = W * H;
+  const int p = p0 + lane;
+  const unsigned long long all = span_entries(r, ng + ns, W, H, p0, lane);
+  const unsigned long long gmask = ng < 64 ? all & ((1ull << ng) - 1ull) : all, smask = ng < 64 ? all >> ng : 0ull;
+  const int row = p / W, col = p - row * W;
+  const float fc = (float)col, fr = (float)row;
+  float d[3];
+  pixel_ray(cam, fc, fr, d);
+  // nearest_hit's loop, statement for statement (the same entry_hit calls in the same order, so the
+  // same best), which also keeps the entries that crossed within LABEL_TIE of the nearest so far;
+  // a crossing more than LABEL_TIE in front of all before it (each >= best) drops them.  What is
+  // left holds every entry within LABEL_TIE of the final best: mostly the hit alone
+  float best = 3.0e38f;
+  int hit = -1;
+  unsigned long long cand = 0ull;
+  for (unsigned long long mk = gmask; mk; mk &= mk - 1ull) {
+    const int g = __builtin_ctzll(mk);
+    const float t = entry_hit(r, g, cam, d, fc, fr, best);
+    if (t >= 0.f && t < best + LABEL_TIE) cand = (t + LABEL_TIE < best ? 0ull : cand) | 1ull << g;
+    if (t >= 0.f && t < best) { best = t; hit = g; }
+  }
+  if (depth && p < np) depth[p] = best < 1.0e38f ? best * dot3(d, cam + 3) : cam[16];
+  float front = best;
+  if (hit >= 0 && ((cand & (cand - 1ull)) || ns > 0)) {   // sites are compared with entry_near's crossing
+    const int coarse = hit;
+    hit = -1;
+    front = 3.0e38f;
+    unsigned long long mk = cand;
+    while (mk) {
+      const int g = __builtin_ctzll(mk);
+      mk &= mk - 1ull;
+      const float t = entry_near(r, g, cam, d, fc, fr, g == coarse ? 3.0e38f : best + LABEL_TIE);
+      if (t >= 0.f && t < front - LABEL_EPS * front) { front = t; hit = g; }
+    }
+    if (hit < 0) { hit = coarse; front = best; }   // grazing: the moved origin misses what the camera's just hit
+  }
+  unsigned long long mk = smask;
+  while (mk) {
+    const int g = ng + __builtin_ctzll(mk);
+    mk &= mk - 1ull;
+    const float t = entry_near(r, g, cam, d, fc, fr, front);
+    if (t >= 0.f && t < front - LABEL_EPS * front) { front = t; hit = g; }
+  }
+  if (p < np) out[p] = hit >= 0 ? lut[hit] : background;
+}
+
 // ---------------------------------------------------------------------------------------
 // colour: Phong shading of the nearest opaque geom, visible sites blended over it
-constexpr int MAXSITEHIT = 4;        // translucent crossings kept per ray (the nearest)
+constexpr int MAXSITEHIT = 4;       // translucent crossings kept per ray (the nearest)
 
 struct RColors {
   float col[MAXRG][COL_W];

@@ -250,6 +250,41 @@ class AdroitVecEnv:
         self.sim.render_rgb(out, self._cam, ss=ss, depth=depth_out)
         return out
 
+    def render_segmentation(self, cameras=None, width: int = 64, height: int = 64, kind: str = "geom", lut=None,
+                            background: int = -1, sites: bool = False, env_ids=None, depth: bool = False, out=None,
+                            depth_out=None, env_cams=None):
+        """Segmentation frames of every env's current state (``aw_render_labels``): per pixel an
+        int32 label of what the camera sees there, ``background`` where it sees nothing.
+        ``cameras``: the items ``render_views`` takes, a list of them or one of them (then the view
+        axis is dropped); None: the reference's free camera.  ``kind``: ``"entry"``, ``"geom"``
+        (model geom id), ``"body"`` (model body id) or ``"mujoco"`` (``objtype << 16 | objid``), or
+        ``lut``: an int table over the render entries (``mj_envs_amd.labels``: ``label_table``,
+        ``body_classes``).  ``sites``: the visible sites (goal markers) are drawn too, solid.
+        ``env_ids`` (device int32 [n], a list or None = all): only these envs, in this order;
+        ``env_cams`` stays [N, V, 17], indexed by env id.  Returns labels [n, V, height, width]
+        (int32, device), with ``depth`` the pair (labels, depth frames [n, V, height, width])."""
+        import torch
+        from .labels import label_table
+        single = cameras is None or not isinstance(cameras, list)
+        cams = ["free" if cameras is None else cameras] if single else cameras
+        views = [self._view(c, width, height) for c in cams]
+        if lut is None:
+            lut = label_table(self.model, kind)
+        if env_ids is not None and not isinstance(env_ids, torch.Tensor):
+            env_ids = torch.as_tensor(np.asarray(env_ids, np.int32), device=self.sim.torch_device)
+        n, nv = self.num_envs if env_ids is None else int(env_ids.shape[0]), len(views)
+        if out is None:
+            out = self.sim.empty(n, nv, height, width, dtype=torch.int32)
+        if depth and depth_out is None:
+            depth_out = self.sim.empty(n, nv, height, width)
+        shape = (n, nv, height, width)
+        self.sim.render_labels(views, width, height, out.view(shape), depth=depth_out.view(shape) if depth else None,
+                               env_cam=env_cams, env_ids=env_ids, lut=lut, background=background, sites=int(bool(sites)))
+        if single:
+            out = out.view(n, height, width)
+            depth_out = depth_out.view(n, height, width) if depth else None
+        return (out, depth_out) if depth else out
+
     # --- state -----------------------------------------------------------------------------
     def get_state(self) -> Dict[str, "object"]:
         s = self.sim
@@ -429,8 +464,14 @@ class _AdroitEnv(_reference_base()):
         if mode == "rgb":
             size, ss = (64, 2) if enable_resize else (128, 1)
             return self.vec.render_rgb(size, size, ss=ss, camera=camera)[0].cpu().numpy().astype(np.float64)
+        if mode == "segmentation":
+            # mujoco-py's sim.render(..., segmentation=True): [H, W, 2] int32, channel 0 the mjtObj type
+            # (geom 5, site 6), channel 1 the object id, -1 / -1 where nothing is seen; sites included
+            from .labels import unpack_mujoco
+            seg = self.vec.render_segmentation(camera, self.width, self.height, kind="mujoco", sites=True)[0]
+            return np.stack(unpack_mujoco(seg.cpu().numpy()), axis=-1).astype(np.int32)
         if mode != "depth":
-            raise ValueError(f"render: mode must be 'depth' or 'rgb', not {mode!r}")
+            raise ValueError(f"render: mode must be 'depth', 'rgb' or 'segmentation', not {mode!r}")
         return self.vec.render_depth(self.width, self.height, camera=camera)[0].cpu().numpy().astype(np.float64)
 
     # pen's flag (pen_v0.py:23, read by its mj_viewer_headless_setup, :174-177)

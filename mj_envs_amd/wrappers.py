@@ -12,7 +12,8 @@
   ``[N, 1, H, W]``; with ``render_kwargs={"mode": "rgb", "ss": 2}`` the colour frame
   ``[N, H, W, 3]`` float32 in 0..255 (Phong-shaded primitives, the hand's collision proxies in
   its mesh material's colour, the goal-marker sites blended in; parity-unpinned against the
-  reference's OpenGL frame).
+  reference's OpenGL frame); with ``render_kwargs={"mode": "segmentation", "kind": "body"}`` the
+  label frame ``[N, 1, H, W]`` float32 (``AdroitVecEnv.render_segmentation``).
 * ``SB3VecEnv`` -- the stable-baselines3 ``VecEnv`` method surface (``reset``, ``step_async`` /
   ``step_wait``, ``step``, ``get_attr`` / ``set_attr`` / ``env_method``, ``env_is_wrapped``,
   ``seed``, ``close``, ``num_envs``, spaces) without importing SB3; numpy out as SB3 expects
@@ -64,8 +65,12 @@ class PixelObservationVecEnv:
         self.obs_key = obs_key
         self.width, self.height = int(rk.get("width", 64)), int(rk.get("height", 64))
         self.mode, self.ss = rk.get("mode", "depth"), int(rk.get("ss", 1))
-        if self.mode not in ("depth", "rgb"):
-            raise ValueError(f"render_kwargs['mode'] must be 'depth' or 'rgb', not {self.mode!r}")
+        if self.mode not in ("depth", "rgb", "segmentation"):
+            raise ValueError(f"render_kwargs['mode'] must be 'depth', 'rgb' or 'segmentation', not {self.mode!r}")
+        # mode "segmentation": render_kwargs["kind"] / ["lut"] / ["background"] / ["sites"] as
+        # AdroitVecEnv.render_segmentation takes them; the labels as float32, shaped like depth
+        self.seg_kwargs = dict(kind=rk.get("kind", "geom"), lut=rk.get("lut"), background=int(rk.get("background", -1)),
+                               sites=bool(rk.get("sites", False)))
         # render_kwargs["camera"]: a model camera's name, a (record, body) pair or "free" -- or a list
         # of those, rendered in one launch as [N, V, ...]; render_kwargs["env_cams"]: per-env records
         # [N, V, 17] (AdroitVecEnv.render_views).  Without the key: the reference's free camera.
@@ -83,12 +88,13 @@ class PixelObservationVecEnv:
         self._pixels_fresh = False
         self.action_space = env.action_space
         self.state_space = env.observation_space
+        lo = -np.inf if self.mode == "segmentation" else 0.0      # labels: whatever the table holds
         self.pixel_space = Box(0.0, 255.0, (self.height, self.width, 3)) if self.mode == "rgb" \
-            else Box(0.0, np.inf, (1, self.height, self.width))
+            else Box(lo, np.inf, (1, self.height, self.width))
         if self.multi_view:
             nv = len(self.cameras)
             self.pixel_space = Box(0.0, 255.0, (nv, self.height, self.width, 3)) if self.mode == "rgb" \
-                else Box(0.0, np.inf, (nv, self.height, self.width))
+                else Box(lo, np.inf, (nv, self.height, self.width))
         self.observation_space = self.pixel_space if obs_key == PIXELS_KEY else self.state_space
 
     # --- observations --------------------------------------------------------------------
@@ -101,7 +107,16 @@ class PixelObservationVecEnv:
     def get_pixels(self):
         if not self._pixels_fresh:
             n, h, w = self.num_envs, self.height, self.width
-            if self.cameras is not None:
+            if self.mode == "segmentation":
+                nv = 1 if self.cameras is None else len(self.cameras)
+                if self._pixels is None:
+                    import torch
+                    self._seg32 = self.env.sim.empty(n, nv, h, w, dtype=torch.int32)   # what the kernel writes
+                    self._pixels = self.env.sim.empty(n, nv, h, w)
+                self.env.render_segmentation(["free"] if self.cameras is None else self.cameras, w, h,
+                                             env_cams=self.env_cams, out=self._seg32, **self.seg_kwargs)
+                self._pixels.copy_(self._seg32)                                      # float32 labels
+            elif self.cameras is not None:
                 self._render_cameras(n, h, w)
             elif self.mode == "rgb":
                 if self._pixels is None:
@@ -266,8 +281,10 @@ def make_env(config, num_envs: int = 1, device: int = 0):
     """``utils/helpers.py:56-78`` make_env for the Adroit suite, batched: ``config.env_name``,
     ``config.variation_type``, ``config.state_type`` ('observation' -> pixels, 'vector' ->
     state), ``config.nogui`` (False: the GUI wrapper, state tensors, no pixels); optional
-    ``config.pixel_mode``: ``"depth"`` (default) or ``"rgb"`` (colour pixels, 2x2 rays per pixel:
-    the reference's resized frame); optional ``config.camera``: the pixels' camera -- a model
+    ``config.pixel_mode``: ``"depth"`` (default), ``"rgb"`` (colour pixels, 2x2 rays per pixel:
+    the reference's resized frame) or ``"segmentation"`` (label pixels shaped like depth; optional
+    ``config.segmentation_kind`` -- "geom", "body", "entry", "mujoco" -- and
+    ``config.segmentation_sites``); optional ``config.camera``: the pixels' camera -- a model
     camera's name, a ``(record, body)`` pair or a list of those (``render_kwargs["camera"]``;
     default: the reference's free camera); optional ``config.sensors``: MuJoCo's sensordata in
     ``info["sensordata"]`` of every step (``AdroitVecEnv(sensors=True)``); optional ``config.data``
@@ -283,6 +300,9 @@ def make_env(config, num_envs: int = 1, device: int = 0):
     mode = getattr(config, "pixel_mode", "depth") or "depth"
     if mode == "rgb":
         rk.update(mode="rgb", ss=2)
+    elif mode == "segmentation":
+        rk.update(mode="segmentation", kind=getattr(config, "segmentation_kind", "geom") or "geom",
+                  sites=bool(getattr(config, "segmentation_sites", False)))
     elif mode != "depth":
         raise Exception(f"Unsupported pixel mode '{mode}'")
     if getattr(config, "camera", None) is not None:
