@@ -334,6 +334,51 @@ int aw_render_labels(aw_handle* h, const aw_view* views, int nviews, const float
                      const int32_t* env_ids, int n_sel, const int32_t* lut, int32_t background,
                      int sites, int width, int height, int32_t* labels, float* depth, void* stream);
 
+/* Point-cloud observations: a fixed-size 3D cloud per env from the depth cameras -- every pixel
+ * unprojected into the world, cropped to a box, filtered by what it shows, the views merged
+ * (aw_render_cloud), then farthest-point-sampled down to npoints (aw_cloud_fps).
+ *   aw_render_cloud takes views, nviews, env_cam, env_ids / n_sel, sites, width and height as
+ * aw_render_labels does and writes the candidate points of output row k (env env_ids[k], or env k).
+ * A pixel is a candidate when (1) its ray hits a render entry -- aw_render_labels' search and tie
+ * rules, so the hit mask and the entry are bit for bit those of aw_render_labels with lut NULL --
+ * (2) keep[entry] != 0 and (3) the fp32 world point cam_pos + t*d (d the pixel's unit ray; t for a
+ * geom the crossing the depth frame of aw_render_labels is written from, so depth = (p - cam_pos) .
+ * forward to a few fp32 roundings: the cloud is that depth frame unprojected; for a site, which
+ * writes no depth, the site's own crossing) lies inside the closed box.  Candidates are stored in ascending flat
+ * pixel index v*height*width + row*width + col, whatever the schedule (no atomics).
+ *   keep: HOST array of ngeom + nsite bytes (aw_render_entries), or NULL = every entry is kept;
+ * mj_envs_amd/labels.py keep_table builds one from body names.  box: HOST array of 6 floats, lo xyz
+ * then hi xyz, world frame, or NULL = no crop.  frame_body: 0 = the stored points are world
+ * coordinates; a body id b = they are rot(xquat[b])^T (p - xpos[b]), the env's own body frame of
+ * this render (the crop is still tested on the world point).  cap: 1..AW_CLOUD_MAXCAND slots per row.
+ *   xyz: DEVICE [n][cap][3] fp32.  pix: DEVICE [n][cap] int32 or NULL, the candidate's flat pixel
+ * index: colours and labels of a cloud are a gather from aw_render_views / aw_render_labels frames
+ * of the same views.  count: DEVICE [n] int32, the row's number of candidates, which may exceed cap;
+ * only the first min(count, cap) are stored and the slots past them are left untouched.  An env id
+ * outside [0, N) leaves its row untouched, count included.
+ * AW_EINVAL: as aw_render_labels (NULL xyz or count in place of NULL labels), cap outside
+ * 1..AW_CLOUD_MAXCAND, frame_body outside [0, nbody), a box with lo > hi (or a NaN) on an axis.
+ * AW_EUNSUPPORTED: sites 1 on a model table without the appearance arrays.
+ *   aw_cloud_fps is stateless (no handle): rows xyz [n][cap][3] with count [n] candidates each ->
+ * out_xyz [n][npoints][3] and out_idx [n][npoints] int32 (or NULL), all DEVICE.  With c = min(count,
+ * cap) (a negative count is 0): selection 0 is candidate 0; selection k < min(npoints, c) is the
+ * candidate with the largest minimum squared distance to selections 0..k-1, the lowest index on a
+ * tie; slots k >= c repeat selection k mod c; with c == 0 the row is zeros and out_idx -1.  The
+ * squared distance is (dx*dx + dy*dy) + dz*dz with every difference, product and sum an individually
+ * rounded fp32 operation (no fused multiply-add; denormals flushed), so an fp32 restatement on the
+ * host reproduces the choice bit for bit (tests/cloud_checker.py).  out_xyz is a bitwise copy of the
+ * chosen candidates.  Coordinates are expected finite.
+ * AW_EINVAL: n < 1, cap outside 1..AW_CLOUD_MAXCAND, npoints outside 1..AW_FPS_MAXPOINTS, NULL xyz,
+ * count or out_xyz. */
+#define AW_CLOUD_MAXCAND 8192
+#define AW_FPS_MAXPOINTS 1024
+int aw_render_cloud(aw_handle* h, const aw_view* views, int nviews, const float* env_cam,
+                    const int32_t* env_ids, int n_sel, const uint8_t* keep, const float* box,
+                    int frame_body, int sites, int width, int height, int cap, float* xyz, int32_t* pix,
+                    int32_t* count, void* stream);
+int aw_cloud_fps(int n, int cap, const float* xyz, const int32_t* count, int npoints, float* out_xyz,
+                 int32_t* out_idx, void* stream);
+
 /* On-device Gaussian MLP policy: mjrl gaussian_mlp.MLP as used by the
  * reference's DAPG baseline (algos/baselines.py:67-86, hidden_sizes=(32, 32)) -- two tanh
  * hidden layers of width `hidden` (32 or 64), in/out affine transforms, and with sample != 0

@@ -69,6 +69,8 @@ class DataBufs(ctypes.Structure):
 
 
 AW_MAX_VIEWS = 4
+AW_CLOUD_MAXCAND = 8192      # candidate slots per row (aw_render_cloud, aw_cloud_fps)
+AW_FPS_MAXPOINTS = 1024      # sampled points per row (aw_cloud_fps)
 
 
 class View(ctypes.Structure):
@@ -167,6 +169,12 @@ def load():
         L.aw_render_labels.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
                                        ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]
         L.aw_render_labels.restype = ctypes.c_int
+    if hasattr(L, "aw_render_cloud"):
+        L.aw_render_cloud.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp] + \
+            [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp]
+        L.aw_render_cloud.restype = ctypes.c_int
+        L.aw_cloud_fps.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]
+        L.aw_cloud_fps.restype = ctypes.c_int
     if hasattr(L, "aw_policy_mlp"):
         L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, _vp]
@@ -186,7 +194,8 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
            "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_render_rgb",
-           "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_policy_mlp",
+           "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_render_cloud", "aw_cloud_fps",
+           "aw_policy_mlp",
            "aw_collide_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
@@ -249,6 +258,39 @@ def _ptr(t) -> Optional[int]:
 def _stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def cloud_fps(xyz, count, out_xyz, out_idx=None, cap: Optional[int] = None, npoints: Optional[int] = None):
+    """Farthest-point sampling of every row (include/adroit_wave.h aw_cloud_fps; stateless): xyz
+    [n, cap, 3] (device, fp32) with count [n] (device, int32) candidates per row -> out_xyz
+    [n, P, 3] (device, fp32) and optionally out_idx [n, P] (device, int32).  Selection 0 is
+    candidate 0, each further one the candidate farthest from those chosen (lowest index on a tie);
+    rows shorter than P repeat cyclically, an empty row is zeros / -1.  cap, npoints: handed to the
+    library in place of the tensors' dimensions."""
+    import torch
+    for t, what in ((xyz, "xyz"), (out_xyz, "out_xyz")):
+        assert t is None or (t.dim() == 3 and t.shape[2] == 3 and t.dtype == torch.float32 and t.is_contiguous()
+                             and t.is_cuda), f"cloud_fps: {what} must be a device fp32 [n, ., 3]"
+    n = int(count.shape[0]) if count is not None else int(xyz.shape[0])
+    if cap is None:
+        cap = int(xyz.shape[1])
+    if npoints is None:
+        npoints = int(out_xyz.shape[1])
+    if xyz is not None:
+        assert xyz.shape[0] == n and (cap == xyz.shape[1] or not 1 <= cap <= AW_CLOUD_MAXCAND), \
+            "cloud_fps: cap is xyz's second dimension"
+    if out_xyz is not None:
+        assert out_xyz.shape[0] == n and (npoints == out_xyz.shape[1] or not 1 <= npoints <= AW_FPS_MAXPOINTS), \
+            "cloud_fps: npoints is out_xyz's second dimension"
+    if count is not None:
+        assert count.dim() == 1 and count.dtype == torch.int32 and count.is_contiguous() and count.is_cuda, \
+            "cloud_fps: count must be a device int32 vector"
+    if out_idx is not None:
+        assert out_xyz is not None and tuple(out_idx.shape) == tuple(out_xyz.shape[:2]) and \
+            out_idx.dtype == torch.int32 and out_idx.is_contiguous() and out_idx.is_cuda, \
+            "cloud_fps: out_idx must be a device int32 [n, P]"
+    _check(load().aw_cloud_fps(n, int(cap), _ptr(xyz), _ptr(count), int(npoints), _ptr(out_xyz), _ptr(out_idx),
+                               _stream()))
 
 
 class Sim:
@@ -518,6 +560,61 @@ class Sim:
         _check(load().aw_render_labels(self.h, arr, nv, _ptr(env_cam), _ptr(env_ids), n if n_sel is None else int(n_sel),
                                        None if lt is None else lt.ctypes.data, int(background), int(sites), w, h,
                                        _ptr(labels), _ptr(depth), _stream()))
+
+    def render_cloud(self, views, width: int, height: int, xyz, count, pix=None, keep=None, box=None,
+                     frame_body: int = 0, sites=0, env_cam=None, env_ids=None, cap: Optional[int] = None,
+                     n_sel: Optional[int] = None):
+        """Point-cloud candidates of every view in one launch (include/adroit_wave.h aw_render_cloud):
+        the pixels that hit a kept render entry inside the crop box, unprojected, in ascending flat
+        pixel order.  views, env_cam, env_ids, sites, n_sel: as in render_labels.  xyz [n, cap, 3]
+        (device, fp32), count [n] (device, int32: the row's candidates, possibly more than cap) and
+        optionally pix [n, cap] (device, int32: flat pixel index v * H * W + row * W + col).
+        keep: host bytes, one per render entry (None: all kept); box: 6 host floats, lo xyz then hi
+        xyz in the world frame (None: no crop); frame_body: the body whose frame the stored points
+        are expressed in (0: the world).  cap: the capacity handed to the library (default, and the
+        only one it accepts: xyz's second dimension)."""
+        import torch
+        nv = len(views)
+        w, h = int(width), int(height)
+        arr = (View * max(nv, 1))()
+        for k, (rec, body) in enumerate(views):
+            c = np.ascontiguousarray(rec, np.float32)
+            assert c.size == 17, "render_cloud: a camera record has 17 floats"
+            arr[k].rec[:] = c.ravel().tolist()
+            arr[k].body = int(body)
+        n = self.n_envs
+        if env_ids is not None:
+            assert env_ids.dim() == 1 and env_ids.dtype == torch.int32 and env_ids.is_contiguous() and \
+                env_ids.is_cuda, "render_cloud: env_ids must be a device int32 vector"
+            n = int(env_ids.shape[0])
+        if xyz is not None:
+            assert xyz.dim() == 3 and xyz.shape[0] == n and xyz.shape[2] == 3 and xyz.dtype == torch.float32 and \
+                xyz.is_contiguous(), "render_cloud: xyz must be fp32 [n, cap, 3]"
+            if cap is None:
+                cap = int(xyz.shape[1])
+            # a cap the library refuses may be handed through; one it accepts is the row stride it writes with
+            assert cap == xyz.shape[1] or not 1 <= cap <= AW_CLOUD_MAXCAND, "render_cloud: cap is xyz's second dimension"
+        if count is not None:
+            assert tuple(count.shape) == (n,) and count.dtype == torch.int32 and count.is_contiguous(), \
+                "render_cloud: count must be int32 [n]"
+        if pix is not None:
+            assert xyz is not None and tuple(pix.shape) == tuple(xyz.shape[:2]) and pix.dtype == torch.int32 and \
+                pix.is_contiguous(), "render_cloud: pix must be int32 [n, cap]"
+        if env_cam is not None:
+            assert tuple(env_cam.shape) == (self.n_envs, nv, 17) and env_cam.dtype == torch.float32 and \
+                env_cam.is_contiguous(), "render_cloud: env_cam must be fp32 [n_envs, V, 17]"
+        kp = bx = None
+        if keep is not None:
+            kp = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+            assert kp.ndim == 1 and kp.size == sum(self.render_entries()), \
+                "render_cloud: keep has one byte per render entry"
+        if box is not None:
+            bx = np.ascontiguousarray(box, np.float32).ravel()
+            assert bx.size == 6, "render_cloud: box has 6 floats (lo xyz, hi xyz)"
+        _check(load().aw_render_cloud(self.h, arr, nv, _ptr(env_cam), _ptr(env_ids), n if n_sel is None else int(n_sel),
+                                      None if kp is None else kp.ctypes.data, None if bx is None else bx.ctypes.data,
+                                      int(frame_body), int(sites), w, h, 0 if cap is None else int(cap), _ptr(xyz),
+                                      _ptr(pix), _ptr(count), _stream()))
 
     def collide_test(self, types, pos, mat, size, margin, fp64: bool = False):
         """narrowphase of n primitive pairs (test hook): list of arrays [(dist, pos[3], normal[3]), ...]

@@ -129,6 +129,87 @@ __global__ void k_random_actions(int n, int nu, uint64_t seed, uint64_t step, ui
   }
 }
 
+// Farthest-point sampling (aw_cloud_fps): one workgroup of T threads per row, instantiated per
+// capacity class CAP >= cap so that a small cloud does not claim a large cloud's LDS.  The row's
+// c = min(count, cap) candidates are staged in LDS once (the selected point of every iteration is
+// read from there by all threads, one broadcast address); thread t owns the kc = ceil(c / T) <= K =
+// CAP / T consecutive candidates [t kc, (t + 1) kc) -- the work follows the row's count, not its
+// capacity -- and keeps their coordinates and minimum squared distances in registers.  Owning
+// consecutive candidates makes the lowest index of a tie the lowest j within a thread, then the
+// lowest lane, then the lowest wave, so the argmax carries no index through the reductions: per
+// iteration every thread folds the last selection into its kc minima and takes their maximum
+// (strict >: the lowest j), wave_max (DPP) gives the wave's maximum, the lowest lane of the ballot
+// that holds it the wave's index; lane 0 leaves both in LDS, and behind the iteration's one barrier
+// every wave repeats the same step over the NW wave results (lane w reads wave w's pair, the index
+// comes back through readlane: one LDS round trip).  The wave results are double buffered by
+// iteration parity, as k_cloud's counts are.  Slots past c (minimum -1, below every distance)
+// never win while c >= 1.  The distance is (dx dx + dy dy) + dz dz in individually rounded fp32
+// operations, so the choice is reproducible on the host bit for bit (the library flushes fp32
+// denormals: squared distances below 1.2e-38 count as 0).  T is small where several rows fit a
+// CU's LDS (their latency chains overlap) and 1024 where one row fills it.
+template <int CAP, int T>
+__global__ void __launch_bounds__(T) k_fps(int cap, int P, const float* __restrict__ xyz, const int* __restrict__ count,
+                                           float* __restrict__ out_xyz, int* __restrict__ out_idx) {
+  constexpr int K = CAP / T, NW = T / 64;
+  static_assert(CAP % T == 0 && T % 64 == 0 && NW <= 64, "k_fps: whole waves, whole candidates per thread");
+  __shared__ float pts[CAP * 3];
+  __shared__ int sel[AW_FPS_MAXPOINTS];
+  __shared__ float wv[2][NW];
+  __shared__ int wi[2][NW];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = min(max(count[row], 0), cap);   // uniform over the block, and so is every barrier below
+  const float* src = xyz + (size_t)row * cap * 3;
+  for (int i = tid; i < 3 * c; i += T) pts[i] = src[i];
+  if (tid == 0) sel[0] = 0;
+  __syncthreads();
+  const int kc = (c + T - 1) / T;   // <= K, as c <= cap <= CAP
+  float px[K], py[K], pz[K], md[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const int i = tid * kc + j;
+    const bool own = j < kc && i < c;
+    px[j] = own ? pts[3 * i] : 0.f;
+    py[j] = own ? pts[3 * i + 1] : 0.f;
+    pz[j] = own ? pts[3 * i + 2] : 0.f;
+    md[j] = own ? __builtin_inff() : -1.f;
+  }
+  const int m = min(P, c);
+  int cur = 0;
+  for (int k = 1; k < m; k++) {
+    const float sx = pts[3 * cur], sy = pts[3 * cur + 1], sz = pts[3 * cur + 2];
+    float bv = -2.f;
+    int bi = 0;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      if (j < kc) {   // uniform over the block
+        const float dx = __fsub_rn(px[j], sx), dy = __fsub_rn(py[j], sy), dz = __fsub_rn(pz[j], sz);
+        const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+        md[j] = fminf(md[j], d);
+        if (md[j] > bv) { bv = md[j]; bi = tid * kc + j; }
+      }
+    }
+    const float wm = wave_max(bv);
+    const unsigned long long eq = __ballot(bv == wm);
+    const int widx = rlane_i(bi, eq ? __builtin_ctzll(eq) : 0);
+    const int b = k & 1;
+    if (lane == 0) { wv[b][wave] = wm; wi[b][wave] = widx; }
+    __syncthreads();
+    const float cv = lane < NW ? wv[b][lane] : -2.f;
+    const int ci = lane < NW ? wi[b][lane] : 0;
+    const float cm = wave_max(cv);
+    const unsigned long long ceq = __ballot(lane < NW && cv == cm);
+    cur = rlane_i(ci, ceq ? __builtin_ctzll(ceq) : 0);
+    if (tid == 0) sel[k] = cur;
+  }
+  __syncthreads();
+  // selections past c repeat cyclically; an empty row is zeros and index -1
+  for (int j = tid; j < P; j += T) {
+    const int i = c > 0 ? sel[j % c] : -1;
+    if (out_idx) out_idx[(size_t)row * P + j] = i;
+    for (int q = 0; q < 3; q++) out_xyz[((size_t)row * P + j) * 3 + q] = i >= 0 ? pts[3 * i + q] : 0.f;
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // host side
 namespace {
@@ -643,6 +724,61 @@ int aw_render_labels(aw_handle* h, const aw_view* views, int nviews, const float
   for (int e = 0; e < MAXRG; e++) l.v[e] = e < ne && lut ? lut[e] : e;   // and so does the table
   h->ops->labels(h, r, nviews, env_cam, env_ids, env_ids ? n_sel : h->nenv, l, background, sites, width, height, labels,
                  depth, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_render_cloud(aw_handle* h, const aw_view* views, int nviews, const float* env_cam, const int32_t* env_ids,
+                    int n_sel, const uint8_t* keep, const float* box, int frame_body, int sites, int width, int height,
+                    int cap, float* xyz, int32_t* pix, int32_t* count, void* stream) {
+  if (!h || !views || nviews < 1 || nviews > AW_MAX_VIEWS || !xyz || !count || width <= 0 || height <= 0 ||
+      width > 1024 || height > 1024 || (env_ids && n_sel < 1) || (sites != 0 && sites != 1) || cap < 1 ||
+      cap > AW_CLOUD_MAXCAND)
+    return fail(AW_EINVAL, "aw_render_cloud: bad arguments");
+  for (int v = 0; v < nviews; v++)
+    if (views[v].body < 0 || views[v].body >= h->m.nbody)
+      return fail(AW_EINVAL, "aw_render_cloud: a view's body is not a body of the model");
+  if (frame_body < 0 || frame_body >= h->m.nbody)
+    return fail(AW_EINVAL, "aw_render_cloud: frame_body is not a body of the model");
+  for (int k = 0; box && k < 3; k++)
+    if (!(box[k] <= box[3 + k])) return fail(AW_EINVAL, "aw_render_cloud: the box needs lo <= hi on every axis");
+  if (sites && !h->m.appearance)
+    return fail(AW_EUNSUPPORTED, "aw_render_cloud: the model table carries no appearance arrays (no visible sites)");
+  HIPCHK(hipSetDevice(h->device));
+  ViewsRec r = {};
+  for (int v = 0; v < nviews; v++) {
+    memcpy(r.c[v], views[v].rec, sizeof(r.c[v]));   // host array: the records travel as a kernel argument
+    r.body[v] = views[v].body;
+  }
+  CloudRec c = {};
+  const int ne = h->m.nrgeom + h->m.nrsite;
+  for (int e = 0; e < ne; e++)
+    if (!keep || keep[e]) c.keep |= 1ull << e;   // and so do the keep table and the box
+  if (box) memcpy(c.box, box, sizeof(c.box));
+  c.crop = box ? 1 : 0;
+  c.frame_body = frame_body;
+  c.cap = cap;
+  h->ops->cloud(h, r, nviews, env_cam, env_ids, env_ids ? n_sel : h->nenv, c, sites, width, height, xyz, pix, count,
+                (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_cloud_fps(int n, int cap, const float* xyz, const int32_t* count, int npoints, float* out_xyz, int32_t* out_idx,
+                 void* stream) {
+  if (n <= 0 || cap < 1 || cap > AW_CLOUD_MAXCAND || !xyz || !count || npoints < 1 || npoints > AW_FPS_MAXPOINTS ||
+      !out_xyz)
+    return fail(AW_EINVAL, "aw_cloud_fps: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  // the capacity classes: LDS per workgroup 16 / 28 / 52 / 100 KiB
+  if (cap <= 1024)
+    hipLaunchKernelGGL((k_fps<1024, 256>), dim3(n), dim3(256), 0, st, cap, npoints, xyz, count, out_xyz, out_idx);
+  else if (cap <= 2048)
+    hipLaunchKernelGGL((k_fps<2048, 256>), dim3(n), dim3(256), 0, st, cap, npoints, xyz, count, out_xyz, out_idx);
+  else if (cap <= 4096)
+    hipLaunchKernelGGL((k_fps<4096, 512>), dim3(n), dim3(512), 0, st, cap, npoints, xyz, count, out_xyz, out_idx);
+  else
+    hipLaunchKernelGGL((k_fps<8192, 1024>), dim3(n), dim3(1024), 0, st, cap, npoints, xyz, count, out_xyz, out_idx);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }

@@ -41,6 +41,15 @@ struct ViewsRec {
 struct LutRec {
   int v[MAXRG];
 };
+// the filters of one aw_render_cloud launch (k_cloud): bit e of keep is set where render entry e is
+// kept (MAXRG entries: one mask), the world-frame crop box (lo xyz, hi xyz; crop 0: none), the body
+// whose frame the stored points are expressed in (0: the world) and the row capacity
+struct CloudRec {
+  unsigned long long keep;
+  float box[6];
+  int crop, frame_body, cap;
+};
+static_assert(MAXRG <= 64, "CloudRec::keep holds one bit per render entry");
 
 struct TaskOps;
 struct WideOps;
@@ -115,6 +124,8 @@ struct TaskOps {
                 hipStream_t);
   void (*labels)(aw_handle*, const ViewsRec&, int, const float*, const int32_t*, int, const LutRec&, int32_t, int, int,
                  int, int32_t*, float*, hipStream_t);
+  void (*cloud)(aw_handle*, const ViewsRec&, int, const float*, const int32_t*, int, const CloudRec&, int, int, int,
+                float*, int32_t*, int32_t*, hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 

@@ -1,7 +1,7 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
 // -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_dump, k_depth, k_rgb, k_views,
-// k_labels, k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
+// k_labels, k_cloud, k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
 // k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
 // env-step both tiers run is aw_step.h.
 #ifndef AW_TASK_TU
@@ -447,6 +447,86 @@ __global__ void __launch_bounds__(256) k_labels(DModel m, DState st, int n, View
   }
 }
 
+// point-cloud candidates (aw_render_cloud): k_labels' structure -- the staging and the kinematics
+// once per env, per view compose_view, the pixel boxes and the 64-pixel spans -- keeping, of every
+// pixel that passes render_span_cloud (a hit on a kept entry inside the crop box), the world point
+// and the flat pixel index v H W + p, compacted in ascending pixel order into the first cap slots
+// of output row blockIdx.x.  No atomics: the four waves cast one round of 256 consecutive pixels,
+// each ballots its candidates and leaves the popcount in LDS; behind one barrier a candidate's slot
+// is the running base (the candidates of all earlier rounds and views, carried identically by every
+// thread) + the counts of the lower waves + the candidates on lower lanes.  The counts are double
+// buffered by round parity: a wave writes a buffer again two rounds later, past the barrier that
+// every wave reaches only after it has read it.  The round loop and all its barriers are uniform
+// (a wave whose span starts past the frame contributes 0).  count receives the row's total, which
+// may exceed cap; slots past min(total, cap) are not written.  Env selection and the early return of
+// an id outside [0, n) are k_labels'.
+template <int TASK, bool SITES>
+__global__ void __launch_bounds__(256) k_cloud(DModel m, DState st, int n, ViewsRec views, int nviews,
+                                               const float* __restrict__ env_cam, const int* __restrict__ env_ids,
+                                               CloudRec c, int W, int H, float* xyz, int* pix, int* count) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RGeoms rg;
+  __shared__ float lcam[AW_CAM_FLOATS];
+  __shared__ int wcnt[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
+  if (env < 0 || env >= n) return;
+  if (tid < 64) {
+    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+    wsync();
+    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+    stage_kinematics(m, s, lane);
+  }
+  __syncthreads();
+  const int ns = SITES ? m.nrsite : 0;
+  const int np = W * H;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  float* orow = xyz + (size_t)blockIdx.x * c.cap * 3;
+  int* prow = pix ? pix + (size_t)blockIdx.x * c.cap : nullptr;
+  int base = 0, round = 0;
+  for (int v = 0; v < nviews; v++) {
+    compose_view(s, env_cam ? env_cam + ((size_t)env * nviews + v) * AW_CAM_FLOATS : views.c[v], views.body[v], lcam,
+                 tid);
+    __syncthreads();
+    // the record is uniform over the block: held in scalar registers, as in k_views
+    float cam[AW_CAM_FLOATS];
+    for (int k = 0; k < AW_CAM_FLOATS; k++)
+      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    render_geoms(m, s, rg, cam, tid, 256);
+    if constexpr (SITES) render_sites(m, s, rg, cam, tid, 256);
+    __syncthreads();
+    for (int r0 = 0; r0 < np; r0 += 256, round++) {
+      const int p0 = r0 + wave * 64;
+      float pt[3] = {0.f, 0.f, 0.f};
+      bool in = false;
+      if (p0 < np) in = render_span_cloud(rg, m.nrgeom, ns, cam, c.keep, c.crop ? c.box : nullptr, W, H, p0, lane, pt);
+      const unsigned long long mk = __ballot(in);
+      if (lane == 0) wcnt[round & 1][wave] = __popcll(mk);
+      __syncthreads();
+      int slot = base + __popcll(mk & below);
+      for (int w = 0; w < 4; w++) {
+        const int cw = wcnt[round & 1][w];
+        if (w < wave) slot += cw;
+        base += cw;
+      }
+      if (in && slot < c.cap) {
+        if (c.frame_body > 0) {   // rot(xquat[b])^T (pt - xpos[b]): the rotation by the conjugate
+          const float* q = s.xquat[c.frame_body];
+          const float qc[4] = {q[0], -q[1], -q[2], -q[3]};
+          float dif[3];
+          sub3(dif, pt, s.xpos[c.frame_body]);
+          rotvq(pt, dif, qc);
+        }
+        for (int k = 0; k < 3; k++) orow[(size_t)slot * 3 + k] = pt[k];
+        if (prow) prow[slot] = v * np + p0 + lane;
+      }
+    }
+    __syncthreads();   // the next view overwrites cam and the boxes
+  }
+  if (tid == 0) count[blockIdx.x] = base;
+}
+
 // Claim order for the next k_step launch (longest processing time first): per XCD class c (k_step's
 // env range [n c / 8, n (c + 1) / 8)) the envs are bucketed by their last env-step's shader cycles
 // on a quarter-octave scale and written costliest bucket first into perm (positions of the same
@@ -556,11 +636,22 @@ static void launch_labels(aw_handle* h, const ViewsRec& views, int nviews, const
     hipLaunchKernelGGL((k_labels<TASK, false>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
                        env_cam, env_ids, lut, background, W, H, labels, depth);
 }
+template <int TASK>
+static void launch_cloud(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam, const int32_t* env_ids,
+                         int grid, const CloudRec& c, int sites, int W, int H, float* xyz, int32_t* pix, int32_t* count,
+                         hipStream_t st) {
+  if (sites)
+    hipLaunchKernelGGL((k_cloud<TASK, true>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
+                       env_cam, env_ids, c, W, H, xyz, pix, count);
+  else
+    hipLaunchKernelGGL((k_cloud<TASK, false>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
+                       env_cam, env_ids, c, W, H, xyz, pix, count);
+}
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
-                              launch_labels<TASK>};
+                              launch_labels<TASK>, launch_cloud<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();

@@ -184,23 +184,24 @@ AW_DEV float entry_near(const RGeoms& r, int g, const float* cam, const float* d
   return t >= 0.f ? s + t : -1.f;
 }
 
-// segmentation label (and optionally z-depth) of the 64 pixels [p0, p0 + 64) handled by one wave.
+// what pixel p0 + lane of the 64 pixels [p0, p0 + 64) handled by one wave shows: its render entry
+// (-1: nothing), the unit ray d, the crossing `front` the search ends on, the crossing `near` of
+// nearest_hit's loop (what depth is written from; 3e38: no geom) and optionally the z-depth.
 // Geoms: render_span's search (nearest_hit's loop) says whether the ray hits anything and how deep -- depth
 // is written from it, so it is render_span's depth bit for bit, and a pixel is background exactly
 // where that depth is zfar; among the geoms crossing within LABEL_TIE of it the nearest by
 // entry_near is the label (within LABEL_EPS the lower entry).  Sites (ns > 0): the nearest
 // visible-site crossing in front of that geom replaces it (a geom wins a tie; among sites the
 // nearest, then the lower entry -- "in front of the opaque crossing" as render_span_rgb blends, drawn
-// solid), by entry_near as well.  One dword per lane: lut[entry], or background.
-AW_DEV void render_span_labels(const RGeoms& r, int ng, int ns, const float* cam, const int* lut, int background,
-                               int W, int H, int p0, int lane, int* out, float* depth) {
+// solid), by entry_near as well.
+AW_DEV int span_hit(const RGeoms& r, int ng, int ns, const float* cam, int W, int H, int p0, int lane, float* depth,
+                    float* d, float& front, float& near) {
   const int np = W * H;
   const int p = p0 + lane;
   const unsigned long long all = span_entries(r, ng + ns, W, H, p0, lane);
   const unsigned long long gmask = ng < 64 ? all & ((1ull << ng) - 1ull) : all, smask = ng < 64 ? all >> ng : 0ull;
   const int row = p / W, col = p - row * W;
   const float fc = (float)col, fr = (float)row;
-  float d[3];
   pixel_ray(cam, fc, fr, d);
   // nearest_hit's loop, statement for statement (the same entry_hit calls in the same order, so the
   // same best), which also keeps the entries that crossed within LABEL_TIE of the nearest so far;
@@ -216,7 +217,7 @@ AW_DEV void render_span_labels(const RGeoms& r, int ng, int ns, const float* cam
     if (t >= 0.f && t < best) { best = t; hit = g; }
   }
   if (depth && p < np) depth[p] = best < 1.0e38f ? best * dot3(d, cam + 3) : cam[16];
-  float front = best;
+  front = near = best;
   if (hit >= 0 && ((cand & (cand - 1ull)) || ns > 0)) {   // sites are compared with entry_near's crossing
     const int coarse = hit;
     hit = -1;
@@ -237,7 +238,34 @@ AW_DEV void render_span_labels(const RGeoms& r, int ng, int ns, const float* cam
     const float t = entry_near(r, g, cam, d, fc, fr, front);
     if (t >= 0.f && t < front - LABEL_EPS * front) { front = t; hit = g; }
   }
-  if (p < np) out[p] = hit >= 0 ? lut[hit] : background;
+  return hit;
+}
+// segmentation label (and optionally z-depth) of the span: one dword per lane, lut[entry] of
+// span_hit, or background
+AW_DEV void render_span_labels(const RGeoms& r, int ng, int ns, const float* cam, const int* lut, int background,
+                               int W, int H, int p0, int lane, int* out, float* depth) {
+  float d[3], front, near;
+  const int hit = span_hit(r, ng, ns, cam, W, H, p0, lane, depth, d, front, near);
+  if (p0 + lane < W * H) out[p0 + lane] = hit >= 0 ? lut[hit] : background;
+}
+
+// Point cloud (aw_render_cloud): whether pixel p0 + lane is a candidate -- span_hit finds an entry, the
+// entry's bit of `keep` is set and the world point pt = cam + t d lies inside the closed box (lo xyz,
+// hi xyz; nullptr: no crop).  t: for a geom the crossing the depth frame is written from (`near`), so
+// the cloud is that frame unprojected, the same t a few roundings apart -- `front` is the same
+// crossing wherever one geom is hit alone, and where several cross within LABEL_TIE it is entry_near's
+// re-evaluation, up to nearest_hit's cancellation error (1e-4 m at 4.5 m) away; for a site, which
+// writes no depth, its own crossing `front`.  pt is written either way.
+AW_DEV bool render_span_cloud(const RGeoms& r, int ng, int ns, const float* cam, unsigned long long keep,
+                              const float* box, int W, int H, int p0, int lane, float* pt) {
+  float d[3], front, near;
+  const int hit = span_hit(r, ng, ns, cam, W, H, p0, lane, nullptr, d, front, near);
+  const float t = hit >= ng ? front : near;
+  for (int k = 0; k < 3; k++) pt[k] = cam[k] + t * d[k];
+  bool in = p0 + lane < W * H && hit >= 0 && ((keep >> (hit & 63)) & 1ull) != 0ull;
+  if (box)
+    for (int k = 0; k < 3; k++) in = in && pt[k] >= box[k] && pt[k] <= box[3 + k];
+  return in;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -285,6 +285,58 @@ class AdroitVecEnv:
             depth_out = depth_out.view(n, height, width) if depth else None
         return (out, depth_out) if depth else out
 
+    def render_pointcloud(self, cameras=None, width: int = 64, height: int = 64, num_points: int = 512, crop=None,
+                          keep=None, sites: bool = False, frame=None, env_ids=None, env_cams=None,
+                          max_candidates: int = 4096, return_index: bool = False):
+        """A fixed-size point cloud of every env's current state: the depth pixels of ``cameras``
+        (the items ``render_views`` takes, one or a list of up to 4; None: the free camera)
+        unprojected into the world, cropped, filtered and merged (``aw_render_cloud``), then
+        farthest-point-sampled down to ``num_points`` (``aw_cloud_fps``), all on the device.
+        ``crop``: 6 floats, lo xyz then hi xyz in the world frame, ``"workspace"``
+        (``render.workspace_box``) or None (no crop).  ``keep``: which render entries' pixels become
+        points -- a byte table over the entries (``labels.keep_table``), a list of body names (their
+        subtrees are kept) or None (everything).  ``sites``: the visible sites are drawn too.
+        ``frame``: a body name or id whose frame the points are expressed in (None: the world); the
+        crop is always tested in the world.  ``env_ids``, ``env_cams``: as in ``render_segmentation``.
+        ``max_candidates`` (at most 8192): the candidates kept per env before sampling, in pixel
+        order; a scene with more loses the last ones.
+        Returns ``(points [n, num_points, 3] fp32, count [n] int32)``: ``count`` is the number of
+        candidates the sampler chose from; a row with fewer than ``num_points`` repeats its
+        selections cyclically and an empty one is zeros.  With ``return_index`` also ``index
+        [n, num_points]`` int32: each point's flat pixel index ``v * height * width + row * width +
+        col`` (-1 in an empty row), to gather colours or labels from ``render_views`` /
+        ``render_segmentation`` frames of the same cameras."""
+        import torch
+        from .labels import keep_table
+        from .render import workspace_box
+        single = cameras is None or not isinstance(cameras, list)
+        cams = ["free" if cameras is None else cameras] if single else cameras
+        views = [self._view(c, width, height) for c in cams]
+        if isinstance(crop, str):
+            if crop != "workspace":
+                raise ValueError(f"render_pointcloud: crop must be a box, 'workspace' or None, not {crop!r}")
+            crop = workspace_box(self.env_id, self.model)
+        if isinstance(keep, (list, tuple)) and all(isinstance(k, str) for k in keep):
+            keep = keep_table(self.model, keep)
+        body = 0 if frame is None else (self.model.name2id("body", frame) if isinstance(frame, str) else int(frame))
+        if env_ids is not None and not isinstance(env_ids, torch.Tensor):
+            env_ids = torch.as_tensor(np.asarray(env_ids, np.int32), device=self.sim.torch_device)
+        n = self.num_envs if env_ids is None else int(env_ids.shape[0])
+        cap = int(max_candidates)
+        s = self.sim
+        xyz, count = s.empty(n, cap, 3), torch.zeros(n, dtype=torch.int32, device=s.torch_device)
+        pix = s.empty(n, cap, dtype=torch.int32) if return_index else None
+        s.render_cloud(views, width, height, xyz, count, pix=pix, keep=keep, box=crop, frame_body=body,
+                       sites=int(bool(sites)), env_cam=env_cams, env_ids=env_ids)
+        out = s.empty(n, int(num_points), 3)
+        idx = s.empty(n, int(num_points), dtype=torch.int32) if return_index else None
+        _native.cloud_fps(xyz, count, out, idx)
+        count = count.clamp(max=cap)
+        if not return_index:
+            return out, count
+        index = torch.where(idx >= 0, torch.gather(pix, 1, idx.clamp(min=0).long()), idx)
+        return out, count, index
+
     # --- state -----------------------------------------------------------------------------
     def get_state(self) -> Dict[str, "object"]:
         s = self.sim
@@ -460,7 +512,9 @@ class _AdroitEnv(_reference_base()):
         (headless_observer.py:34-52), float64 [H, W, 3] in 0..255 from the HIP ray caster's shading
         model (mj_envs_amd/render.py; parity-unpinned against the reference's OpenGL frame):
         64x64 with 2x2 rays per pixel when ``enable_resize`` (the reference's resized 128x128 crop),
-        else the 128x128 crop itself."""
+        else the 128x128 crop itself.  ``mode="segmentation"``: mujoco-py's [H, W, 2] (type, id) frame.
+        ``mode="pointcloud"``: the farthest-point-sampled cloud [num_points, 3] of the camera's depth
+        pixels (``AdroitVecEnv.render_pointcloud``; its keywords pass through)."""
         if mode == "rgb":
             size, ss = (64, 2) if enable_resize else (128, 1)
             return self.vec.render_rgb(size, size, ss=ss, camera=camera)[0].cpu().numpy().astype(np.float64)
@@ -470,8 +524,13 @@ class _AdroitEnv(_reference_base()):
             from .labels import unpack_mujoco
             seg = self.vec.render_segmentation(camera, self.width, self.height, kind="mujoco", sites=True)[0]
             return np.stack(unpack_mujoco(seg.cpu().numpy()), axis=-1).astype(np.int32)
+        if mode == "pointcloud":
+            # the sampled cloud [num_points, 3] (float64, metres) of AdroitVecEnv.render_pointcloud, whose
+            # keywords (num_points, crop, keep, sites, frame, max_candidates) pass through
+            pts, _ = self.vec.render_pointcloud(camera, self.width, self.height, **kwargs)
+            return pts[0].cpu().numpy().astype(np.float64)
         if mode != "depth":
-            raise ValueError(f"render: mode must be 'depth', 'rgb' or 'segmentation', not {mode!r}")
+            raise ValueError(f"render: mode must be 'depth', 'rgb', 'segmentation' or 'pointcloud', not {mode!r}")
         return self.vec.render_depth(self.width, self.height, camera=camera)[0].cpu().numpy().astype(np.float64)
 
     # pen's flag (pen_v0.py:23, read by its mj_viewer_headless_setup, :174-177)

@@ -11,7 +11,9 @@ passed through an int32 look-up table; this module builds the tables from a comp
 * ``"mujoco"``  mujoco-py's segmentation pair packed into one int, ``objtype << 16 | objid`` with
   mjtObj geom 5 / site 6 (``unpack_mujoco`` splits it again);
 * ``body_classes(model, roots)``  class k + 1 for what hangs below ``roots[k]`` in the body tree,
-  0 elsewhere: hand / object / table masks.
+  0 elsewhere: hand / object / table masks;
+* ``keep_table(model, roots)``  the byte table of the point-cloud renderer: which entries' pixels
+  become points.
 """
 from __future__ import annotations
 
@@ -84,6 +86,16 @@ def body_classes(model, roots: Sequence[Union[int, str]]) -> np.ndarray:
             b = int(parent[b])
         out.append(cls.get(b, 0))
     return np.array(out, np.int32)
+
+
+def keep_table(model, roots: Sequence[Union[int, str]], drop: bool = False) -> np.ndarray:
+    """uint8 keep table [n entries] of the point-cloud renderer (``aw_render_cloud``,
+    ``AdroitVecEnv.render_pointcloud(keep=...)``): 1 for an entry whose body lies in the subtree of
+    one of ``roots`` (body ids or names), 0 elsewhere -- ``["forearm", "Object"]`` keeps the hand and
+    the object and drops the table, the floor and the wall.  ``drop``: the complement, e.g.
+    ``keep_table(m, ["table"], drop=True)`` keeps everything but the table."""
+    inside = body_classes(model, roots) > 0
+    return (~inside if drop else inside).astype(np.uint8)
 
 
 def names(model, kind: str = "geom") -> dict:

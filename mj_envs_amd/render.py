@@ -50,6 +50,14 @@ riding on a body (``mounted_camera``: an eye-in-hand view on the palm) and one r
 to four views of every env per launch.  ``free_camera`` and the two single-camera entry points
 are unchanged.
 
+Point clouds (``aw_render_cloud`` / ``k_cloud``, ``aw_cloud_fps`` / ``k_fps``;
+``AdroitVecEnv.render_pointcloud``): the depth pixels of up to four of those cameras unprojected into
+the world (``cam + t d`` with the depth frame's own crossing ``t``), cropped to a box
+(``workspace_box``: a default per task, over the table top), filtered by render entry
+(``labels.keep_table``: drop the table and the background), merged in pixel order and
+farthest-point-sampled on the device to a fixed number of points per env, optionally in the frame of
+a body such as the palm.
+
 Reference quirks kept: hammer sets up its observer once, in ``__init__``, while ``obj_bid`` is
 still the placeholder ``-1`` (``hammer_v0.py:15,35-38``), so the elevation uses the LAST body.
 door and relocate construct their observer with placeholder body 0 (``door_v0.py:16,41``,
@@ -207,6 +215,36 @@ def jitter_cameras(record, n: int, rng: np.random.Generator, pos_sigma: float = 
         if (lo, hi) != (1.0, 1.0):
             out[e, 12:16] = rec[12:16] * sc
     return out.astype(np.float32)
+
+
+# point clouds (aw_render_cloud / aw_cloud_fps, AdroitVecEnv.render_pointcloud): how far above the
+# table top the default crop of a task reaches -- door's frame and handle stand 0.70 m tall, the
+# other tasks play out within reach of the raised hand
+WORKSPACE_HEIGHT = {"hammer-v0": 0.6, "door-v0": 0.8, "pen-v0": 0.6, "relocate-v0": 0.6}
+WORKSPACE_CLEARANCE = 0.005        # the box starts this far above the table top: the top itself is cut away
+
+
+def workspace_box(env_id: str, model=None) -> np.ndarray:
+    """Default crop of a task's point cloud: float32 ``[lo xyz, hi xyz]`` in the world frame.  x / y:
+    the extent of the table top (the box geom of body ``table``, 0.9 m square, over which the
+    object's and the target's reset ranges lie); z: from ``WORKSPACE_CLEARANCE`` above the table
+    top, so the top's own pixels fall outside, to ``WORKSPACE_HEIGHT[env_id]`` above it.  The forearm
+    enters through the y-lo face and is cut there.  A convenience: pass any box as ``crop``."""
+    if model is None:
+        from .tasks import load_model
+        model = load_model(env_id)
+    xpos, _, xmat = _kinematics0(model)
+    table = model.name2id("body", "table")
+    tops = [g for g in range(int(model.ngeom)) if int(model.geom_bodyid[g]) == table and int(model.geom_type[g]) == 6]
+    if not tops:
+        raise ValueError(f"workspace_box: {env_id} has no table top (a box geom on body 'table')")
+    g = tops[0]
+    c = xpos[table] + xmat[table] @ model.geom_pos[g]
+    half = np.asarray(model.geom_size[g], np.float64)
+    top = c[2] + half[2]
+    lo = [c[0] - half[0], c[1] - half[1], top + WORKSPACE_CLEARANCE]
+    hi = [c[0] + half[0], c[1] + half[1], top + WORKSPACE_HEIGHT.get(env_id, 0.6)]
+    return np.array(lo + hi, np.float32)
 
 
 def compose_record(record, xpos, xquat) -> np.ndarray:

@@ -13,7 +13,10 @@
   ``[N, H, W, 3]`` float32 in 0..255 (Phong-shaded primitives, the hand's collision proxies in
   its mesh material's colour, the goal-marker sites blended in; parity-unpinned against the
   reference's OpenGL frame); with ``render_kwargs={"mode": "segmentation", "kind": "body"}`` the
-  label frame ``[N, 1, H, W]`` float32 (``AdroitVecEnv.render_segmentation``).
+  label frame ``[N, 1, H, W]`` float32 (``AdroitVecEnv.render_segmentation``); with
+  ``render_kwargs={"mode": "pointcloud", "num_points": 512, "crop": "workspace"}`` the
+  farthest-point-sampled cloud ``[N, num_points, 3]`` of the depth pixels
+  (``AdroitVecEnv.render_pointcloud``).
 * ``SB3VecEnv`` -- the stable-baselines3 ``VecEnv`` method surface (``reset``, ``step_async`` /
   ``step_wait``, ``step``, ``get_attr`` / ``set_attr`` / ``env_method``, ``env_is_wrapped``,
   ``seed``, ``close``, ``num_envs``, spaces) without importing SB3; numpy out as SB3 expects
@@ -65,8 +68,15 @@ class PixelObservationVecEnv:
         self.obs_key = obs_key
         self.width, self.height = int(rk.get("width", 64)), int(rk.get("height", 64))
         self.mode, self.ss = rk.get("mode", "depth"), int(rk.get("ss", 1))
-        if self.mode not in ("depth", "rgb", "segmentation"):
-            raise ValueError(f"render_kwargs['mode'] must be 'depth', 'rgb' or 'segmentation', not {self.mode!r}")
+        if self.mode not in ("depth", "rgb", "segmentation", "pointcloud"):
+            raise ValueError("render_kwargs['mode'] must be 'depth', 'rgb', 'segmentation' or 'pointcloud', "
+                             f"not {self.mode!r}")
+        # mode "pointcloud": render_kwargs["num_points"] / ["crop"] / ["keep"] / ["sites"] / ["frame"] /
+        # ["max_candidates"] as AdroitVecEnv.render_pointcloud takes them; the pixels are the sampled
+        # points [N, num_points, 3], width / height the size of the depth frames they come from
+        self.cloud_kwargs = dict(num_points=int(rk.get("num_points", 512)), crop=rk.get("crop"), keep=rk.get("keep"),
+                                 sites=bool(rk.get("sites", False)), frame=rk.get("frame"),
+                                 max_candidates=int(rk.get("max_candidates", 4096)))
         # mode "segmentation": render_kwargs["kind"] / ["lut"] / ["background"] / ["sites"] as
         # AdroitVecEnv.render_segmentation takes them; the labels as float32, shaped like depth
         self.seg_kwargs = dict(kind=rk.get("kind", "geom"), lut=rk.get("lut"), background=int(rk.get("background", -1)),
@@ -95,6 +105,8 @@ class PixelObservationVecEnv:
             nv = len(self.cameras)
             self.pixel_space = Box(0.0, 255.0, (nv, self.height, self.width, 3)) if self.mode == "rgb" \
                 else Box(lo, np.inf, (nv, self.height, self.width))
+        if self.mode == "pointcloud":
+            self.pixel_space = Box(-np.inf, np.inf, (self.cloud_kwargs["num_points"], 3))
         self.observation_space = self.pixel_space if obs_key == PIXELS_KEY else self.state_space
 
     # --- observations --------------------------------------------------------------------
@@ -107,7 +119,11 @@ class PixelObservationVecEnv:
     def get_pixels(self):
         if not self._pixels_fresh:
             n, h, w = self.num_envs, self.height, self.width
-            if self.mode == "segmentation":
+            if self.mode == "pointcloud":
+                cams = None if self.cameras is None else (self.cameras if self.multi_view else self.cameras[0])
+                self._pixels, self.cloud_count = self.env.render_pointcloud(cams, w, h, env_cams=self.env_cams,
+                                                                            **self.cloud_kwargs)
+            elif self.mode == "segmentation":
                 nv = 1 if self.cameras is None else len(self.cameras)
                 if self._pixels is None:
                     import torch
@@ -284,7 +300,9 @@ def make_env(config, num_envs: int = 1, device: int = 0):
     ``config.pixel_mode``: ``"depth"`` (default), ``"rgb"`` (colour pixels, 2x2 rays per pixel:
     the reference's resized frame) or ``"segmentation"`` (label pixels shaped like depth; optional
     ``config.segmentation_kind`` -- "geom", "body", "entry", "mujoco" -- and
-    ``config.segmentation_sites``); optional ``config.camera``: the pixels' camera -- a model
+    ``config.segmentation_sites``) or ``"pointcloud"`` (the sampled cloud ``[N, config.num_points, 3]``,
+    default 512 points; optional ``config.pointcloud_crop`` -- a box or "workspace" -- and
+    ``config.pointcloud_keep``, as ``AdroitVecEnv.render_pointcloud`` takes them); optional ``config.camera``: the pixels' camera -- a model
     camera's name, a ``(record, body)`` pair or a list of those (``render_kwargs["camera"]``;
     default: the reference's free camera); optional ``config.sensors``: MuJoCo's sensordata in
     ``info["sensordata"]`` of every step (``AdroitVecEnv(sensors=True)``); optional ``config.data``
@@ -303,6 +321,9 @@ def make_env(config, num_envs: int = 1, device: int = 0):
     elif mode == "segmentation":
         rk.update(mode="segmentation", kind=getattr(config, "segmentation_kind", "geom") or "geom",
                   sites=bool(getattr(config, "segmentation_sites", False)))
+    elif mode == "pointcloud":
+        rk.update(mode="pointcloud", num_points=int(getattr(config, "num_points", 512) or 512),
+                  crop=getattr(config, "pointcloud_crop", None), keep=getattr(config, "pointcloud_keep", None))
     elif mode != "depth":
         raise Exception(f"Unsupported pixel mode '{mode}'")
     if getattr(config, "camera", None) is not None:
