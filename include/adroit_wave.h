@@ -187,6 +187,47 @@ int aw_get_state(aw_handle* h, float* qpos, float* qvel, float* warmstart, float
 int aw_set_state(aw_handle* h, const float* qpos, const float* qvel, const float* warmstart,
                  const float* params, float* obs, void* stream);
 
+/* Indexed state access: set, read and clone a subset of the envs on the device (demonstration-state
+ * resets, restarts from a replay buffer, branching one state into the K rollouts of a sampling
+ * planner, broadcasting B root states into a B x K planner batch on another handle).  Every id and
+ * row array is a DEVICE int32 array, as aw_render_labels' env_ids is.
+ *   aw_set_state_ids: env env_ids[k] (k < n_sel) takes row rows[k] (rows == NULL: row k) of every
+ * non-NULL input array -- qpos [n_rows][nq], qvel / warmstart [n_rows][nv], params [n_rows][nparam];
+ * a NULL array keeps that env's current values, and all four NULL re-runs the forward of the
+ * selected envs.  Then mj_forward with ctrl 0 for the selected envs only (n_sel workgroups).  obs:
+ * NULL, or the caller's [N][obs_dim] buffer indexed by ENV id, of which only the selected envs' rows
+ * are written (as aw_reset with a mask writes it).  For a selected env every result -- the stored
+ * state, the obs row, its status (last and sticky), its sensordata row, its mjData-view rows -- is bit
+ * for bit what aw_set_state gives for the same values, the hand-off of a forward beyond the fast
+ * capacities to the wide tier included (aw_set_tier(h, 1) forces it); an env that is not selected is
+ * untouched in every buffer.  reset_episode != 0 zeroes the selected envs' running-episode counters
+ * (steps, return, goal steps: what aw_get_episode's first three report), as aw_reset does; the
+ * finished-episode count (the Philox episode key), the last-episode stats and the totals are never
+ * touched.  A pair whose env_ids[k] is outside [0, N) or whose rows[k] (or k, with rows NULL) is
+ * outside [0, n_rows) is skipped: nothing is written for it.  env_ids must be distinct: the library
+ * does not check it, and an env listed more than once ends in the state of one of its rows,
+ * unspecified which (nothing outside that env is written).  rows may repeat (a broadcast).
+ * AW_EINVAL: NULL handle or env_ids, n_sel < 1, n_rows < 1.
+ *   aw_get_state_ids: output row k (qpos [n_sel][nq], ...) receives env env_ids[k]; an id outside
+ * [0, N) leaves row k untouched; any output may be NULL; ids may repeat.  A plain gather, no forward.
+ * AW_EINVAL: NULL handle or env_ids, n_sel < 1.
+ *   aw_clone_envs: env dst_ids[k] becomes a copy of env src_ids[k] (k < n): qpos, qvel, warmstart,
+ * params and, with episode != 0, the running-episode counters (never the finished-episode count, the
+ * last-episode stats or the totals); then the forward of the dst envs as in aw_set_state_ids (obs as
+ * there).  Every read happens before any write: the n source rows are gathered into a scratch block of
+ * the handle, then set from there on the same stream -- src {0,1}, dst {1,0} swaps two envs, src
+ * {0,0,0}, dst {1,2,3} broadcasts one.  The FIRST call allocates the scratch block (N rows; a
+ * hipMalloc, so not inside a graph capture); aw_destroy frees it.  dst_ids must be distinct (the rule
+ * of env_ids above); src_ids may repeat.  A pair with either id outside [0, N) is skipped whole.
+ * AW_EINVAL: NULL handle, src_ids or dst_ids, n outside 1..N. */
+int aw_set_state_ids(aw_handle* h, const int32_t* env_ids, int n_sel, const int32_t* rows, int n_rows,
+                     const float* qpos, const float* qvel, const float* warmstart, const float* params,
+                     int reset_episode, float* obs, void* stream);
+int aw_get_state_ids(aw_handle* h, const int32_t* env_ids, int n_sel, float* qpos, float* qvel,
+                     float* warmstart, float* params, void* stream);
+int aw_clone_envs(aw_handle* h, const int32_t* src_ids, const int32_t* dst_ids, int n, int episode,
+                  float* obs, void* stream);
+
 /* per-env status flags (AW_ST_*), uint32 [N]: `last` = flags raised by the last step / reset /
  * set_state of each env, `sticky` = OR of every flag raised since aw_create or the last
  * aw_clear_status (MuJoCo's warning counters play this role); either pointer may be NULL */

@@ -175,6 +175,13 @@ def load():
         L.aw_render_cloud.restype = ctypes.c_int
         L.aw_cloud_fps.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]
         L.aw_cloud_fps.restype = ctypes.c_int
+    if hasattr(L, "aw_set_state_ids"):
+        L.aw_set_state_ids.argtypes = [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                       _vp, _vp]
+        L.aw_get_state_ids.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]
+        L.aw_clone_envs.argtypes = [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]
+        for f in ("aw_set_state_ids", "aw_get_state_ids", "aw_clone_envs"):
+            getattr(L, f).restype = ctypes.c_int
     if hasattr(L, "aw_policy_mlp"):
         L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, _vp]
@@ -190,7 +197,8 @@ def load():
 
 EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier", "aw_set_fault", "aw_reset", "aw_step",
            "aw_set_sensors", "aw_sensor_count", "aw_sensordata", "aw_set_data",
-           "aw_random_actions", "aw_set_env_offset", "aw_get_state", "aw_set_state", "aw_status",
+           "aw_random_actions", "aw_set_env_offset", "aw_get_state", "aw_set_state", "aw_set_state_ids",
+           "aw_get_state_ids", "aw_clone_envs", "aw_status",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
            "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_render_rgb",
@@ -258,6 +266,31 @@ def _ptr(t) -> Optional[int]:
 def _stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def check_ids(ids, n: int, name: str = "env_ids", distinct: bool = True) -> np.ndarray:
+    """Env ids (or rows) given on the host -- a list or a numpy array -- as a checked int32 vector:
+    integers, each in [0, n) and (``distinct``) no id twice; ValueError otherwise.  Pure: needs no
+    GPU.  (Ids given as a device int32 tensor are not checked anywhere: reading them would wait
+    for the device; the library skips what is out of range, include/adroit_wave.h aw_set_state_ids.)"""
+    a = np.asarray(ids)
+    if a.ndim != 1 or a.size < 1:
+        raise ValueError(f"{name}: a non-empty one-dimensional list of ids, not shape {a.shape}")
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name}: integer ids, not {a.dtype}")
+    if int(a.min()) < 0 or int(a.max()) >= int(n):
+        bad = a[(a < 0) | (a >= int(n))]
+        raise ValueError(f"{name}: id {int(bad[0])} outside [0, {int(n)})")
+    if distinct and np.unique(a).size != a.size:
+        u, c = np.unique(a, return_counts=True)
+        raise ValueError(f"{name}: id {int(u[c > 1][0])} listed more than once")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _ids_ok(t, what: str):
+    import torch
+    assert t.dim() == 1 and t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda, \
+        f"{what} must be a device int32 vector"
 
 
 def cloud_fps(xyz, count, out_xyz, out_idx=None, cap: Optional[int] = None, npoints: Optional[int] = None):
@@ -417,6 +450,53 @@ class Sim:
     def set_state(self, qpos=None, qvel=None, warm=None, params=None, obs=None):
         _check(load().aw_set_state(self.h, _ptr(qpos), _ptr(qvel), _ptr(warm), _ptr(params), _ptr(obs),
                                    _stream()))
+
+    def _state_rows(self, what, n, qpos, qvel, warm, params):
+        """the state arrays of the indexed calls: device fp32 [n, nq | nv | nv | nparam] or None"""
+        import torch
+        for t, w, k in ((qpos, self.nq, "qpos"), (qvel, self.nv, "qvel"), (warm, self.nv, "warm"),
+                        (params, self.nparam, "params")):
+            assert t is None or (tuple(t.shape) == (n, w) and t.dtype == torch.float32 and t.is_contiguous()
+                                 and t.is_cuda), f"{what}: {k} must be a device fp32 [{n}, {w}]"
+
+    def set_state_ids(self, env_ids, rows=None, n_rows: Optional[int] = None, qpos=None, qvel=None, warm=None,
+                      params=None, reset_episode: bool = False, obs=None):
+        """Set env env_ids[k] from row rows[k] (None: row k) of the given [n_rows, ...] arrays and run
+        its forward (include/adroit_wave.h aw_set_state_ids).  env_ids, rows: device int32 vectors, not
+        validated (the library skips ids and rows out of range; env_ids must be distinct).  obs:
+        [n_envs, obs_dim], indexed by env id; only the selected envs' rows are written."""
+        given = [t for t in (qpos, qvel, warm, params) if t is not None]
+        _ids_ok(env_ids, "set_state_ids: env_ids")
+        n_sel = int(env_ids.shape[0])
+        if rows is not None:
+            _ids_ok(rows, "set_state_ids: rows")
+            assert int(rows.shape[0]) == n_sel, "set_state_ids: one row per env id"
+        if n_rows is None:
+            n_rows = int(given[0].shape[0]) if given else n_sel
+        self._state_rows("set_state_ids", n_rows, qpos, qvel, warm, params)
+        assert obs is None or tuple(obs.shape) == (self.n_envs, self.obs_dim), "set_state_ids: obs is [n_envs, obs_dim]"
+        _check(load().aw_set_state_ids(self.h, _ptr(env_ids), n_sel, _ptr(rows), int(n_rows), _ptr(qpos), _ptr(qvel),
+                                       _ptr(warm), _ptr(params), int(bool(reset_episode)), _ptr(obs), _stream()))
+
+    def get_state_ids(self, env_ids, qpos=None, qvel=None, warm=None, params=None):
+        """row k of the given [n_sel, ...] arrays receives env env_ids[k] (device int32; an id out of
+        range leaves its row as it was): include/adroit_wave.h aw_get_state_ids"""
+        _ids_ok(env_ids, "get_state_ids: env_ids")
+        n_sel = int(env_ids.shape[0])
+        self._state_rows("get_state_ids", n_sel, qpos, qvel, warm, params)
+        _check(load().aw_get_state_ids(self.h, _ptr(env_ids), n_sel, _ptr(qpos), _ptr(qvel), _ptr(warm), _ptr(params),
+                                       _stream()))
+
+    def clone_envs(self, src_ids, dst_ids, episode: bool = True, obs=None):
+        """env dst_ids[k] becomes a copy of env src_ids[k] (device int32 vectors; every read before any
+        write; dst_ids distinct), then the forward of the dst envs: include/adroit_wave.h aw_clone_envs.
+        The first call allocates the handle's scratch block."""
+        _ids_ok(src_ids, "clone_envs: src_ids")
+        _ids_ok(dst_ids, "clone_envs: dst_ids")
+        assert src_ids.shape == dst_ids.shape, "clone_envs: one source per destination"
+        assert obs is None or tuple(obs.shape) == (self.n_envs, self.obs_dim), "clone_envs: obs is [n_envs, obs_dim]"
+        _check(load().aw_clone_envs(self.h, _ptr(src_ids), _ptr(dst_ids), int(src_ids.shape[0]), int(bool(episode)),
+                                    _ptr(obs), _stream()))
 
     def status(self, last=None, sticky=None):
         """per-env flags (ST_*): of the last step (last) / OR since create or clear_status (sticky)"""

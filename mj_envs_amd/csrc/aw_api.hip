@@ -129,6 +129,34 @@ __global__ void k_random_actions(int n, int nu, uint64_t seed, uint64_t step, ui
   }
 }
 
+// The state rows of selected envs (aw_get_state_ids; aw_clone_envs' read pass): one wave per output
+// row, four per workgroup; row k receives env env_ids[k], an id outside [0, n) leaves it untouched.
+// The id is wave-uniform (readfirstlane), so the row bases are scalar.  Any output may be null; the
+// episode outputs are aw_clone_envs' (the running episode's counters).
+__global__ void __launch_bounds__(256) k_get_state_ids(DState st, int n, int nq, int nv, int nparam,
+                                                       const int* __restrict__ env_ids, int n_sel, float* qpos,
+                                                       float* qvel, float* warm, float* params, int* ep_len,
+                                                       float* ep_ret, int* ep_goal) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= n_sel) return;
+  const int env = __builtin_amdgcn_readfirstlane(env_ids[k]);
+  if ((unsigned)env >= (unsigned)n) return;
+  for (int i = lane; i < nq; i += 64)
+    if (qpos) qpos[(size_t)k * nq + i] = st.qpos[(size_t)env * nq + i];
+  for (int i = lane; i < nv; i += 64) {
+    if (qvel) qvel[(size_t)k * nv + i] = st.qvel[(size_t)env * nv + i];
+    if (warm) warm[(size_t)k * nv + i] = st.warm[(size_t)env * nv + i];
+  }
+  for (int i = lane; i < nparam; i += 64)
+    if (params) params[(size_t)k * nparam + i] = st.params[(size_t)env * nparam + i];
+  if (lane == 0) {
+    if (ep_len) ep_len[k] = st.ep_len[env];
+    if (ep_ret) ep_ret[k] = st.ep_ret[env];
+    if (ep_goal) ep_goal[k] = st.ep_goal[env];
+  }
+}
+
 // Farthest-point sampling (aw_cloud_fps): one workgroup of T threads per row, instantiated per
 // capacity class CAP >= cap so that a small cloud does not claim a large cloud's LDS.  The row's
 // c = min(count, cap) candidates are staged in LDS once (the selected point of every iteration is
@@ -296,6 +324,7 @@ static void free_handle(aw_handle* h) {
   if (h->dsens) (void)hipFree(h->dsens);
   if (h->ddata) (void)hipFree(h->ddata);
   if (h->sensordata) (void)hipFree(h->sensordata);
+  if (h->clone_scratch) (void)hipFree(h->clone_scratch);
   delete h;
 }
 
@@ -545,6 +574,59 @@ int aw_set_state(aw_handle* h, const float* qpos, const float* qvel, const float
   if (!h) return fail(AW_EINVAL, "aw_set_state: null");
   HIPCHK(hipSetDevice(h->device));
   h->ops->set(h, qpos, qvel, warm, params, obs, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+static void launch_get_ids(aw_handle* h, const int32_t* env_ids, int n_sel, float* qpos, float* qvel, float* warm,
+                           float* params, int* ep_len, float* ep_ret, int* ep_goal, hipStream_t st) {
+  hipLaunchKernelGGL(k_get_state_ids, dim3((n_sel + 3) / 4), dim3(256), 0, st, h->st, h->nenv, h->m.nq, h->m.nv,
+                     h->m.nparam, env_ids, n_sel, qpos, qvel, warm, h->m.nparam ? params : nullptr, ep_len, ep_ret,
+                     ep_goal);
+}
+
+int aw_set_state_ids(aw_handle* h, const int32_t* env_ids, int n_sel, const int32_t* rows, int n_rows,
+                     const float* qpos, const float* qvel, const float* warm, const float* params, int reset_episode,
+                     float* obs, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_set_state_ids: null");
+  if (!env_ids || n_sel < 1 || n_rows < 1)
+    return fail(AW_EINVAL, "aw_set_state_ids: env_ids must be given, n_sel >= 1 and n_rows >= 1");
+  HIPCHK(hipSetDevice(h->device));
+  const SetIds a = {env_ids, rows, nullptr, n_sel, n_rows, qpos, qvel, warm, h->m.nparam ? params : nullptr,
+                    nullptr, nullptr, nullptr, reset_episode != 0};
+  h->ops->set_ids(h, a, obs, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_get_state_ids(aw_handle* h, const int32_t* env_ids, int n_sel, float* qpos, float* qvel, float* warm,
+                     float* params, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_get_state_ids: null");
+  if (!env_ids || n_sel < 1) return fail(AW_EINVAL, "aw_get_state_ids: env_ids must be given and n_sel >= 1");
+  HIPCHK(hipSetDevice(h->device));
+  launch_get_ids(h, env_ids, n_sel, qpos, qvel, warm, params, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_clone_envs(aw_handle* h, const int32_t* src_ids, const int32_t* dst_ids, int n, int episode, float* obs,
+                  void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_clone_envs: null");
+  if (!src_ids || !dst_ids || n < 1 || n > h->nenv)
+    return fail(AW_EINVAL, "aw_clone_envs: src_ids and dst_ids must be given and n in 1..n_envs");
+  HIPCHK(hipSetDevice(h->device));
+  // the scratch block: nenv rows of qpos, qvel, warmstart, params and the three episode counters
+  const size_t N = (size_t)h->nenv, nq = h->m.nq, nv = h->m.nv, np = h->m.nparam;
+  if (!h->clone_scratch) HIPCHK(hipMalloc(&h->clone_scratch, N * (nq + 2 * nv + np + 3) * sizeof(float)));
+  float* q = (float*)h->clone_scratch;
+  float *v = q + N * nq, *w = v + N * nv, *p = w + N * nv, *er = p + N * np;
+  int32_t *el = (int32_t*)(er + N), *eg = el + N;
+  // every read before any write: the gather ends before the set kernel starts (one stream)
+  launch_get_ids(h, src_ids, n, q, v, w, p, episode ? el : nullptr, episode ? er : nullptr, episode ? eg : nullptr,
+                 (hipStream_t)stream);
+  const SetIds a = {dst_ids, nullptr, src_ids, n, n, q, v, w, np ? p : nullptr,
+                    episode ? el : nullptr, episode ? er : nullptr, episode ? eg : nullptr, 0};
+  h->ops->set_ids(h, a, obs, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }

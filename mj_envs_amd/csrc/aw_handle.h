@@ -51,6 +51,19 @@ struct CloudRec {
 };
 static_assert(MAXRG <= 64, "CloudRec::keep holds one bit per render entry");
 
+// the selection and the inputs of one k_set_state_ids launch (aw_set_state_ids, aw_clone_envs): device
+// arrays; env env_ids[k] takes row rows[k] (nullptr: row k) of the non-null state and episode arrays;
+// also_ids (nullptr, or aw_clone_envs' source ids): a pair is skipped when also_ids[k] is no env
+struct SetIds {
+  const int32_t *env_ids, *rows, *also_ids;
+  int n_sel, n_rows;
+  const float *qpos, *qvel, *warm, *params;
+  const int32_t* ep_len;
+  const float* ep_ret;
+  const int32_t* ep_goal;
+  int reset_episode;
+};
+
 struct TaskOps;
 struct WideOps;
 struct aw_handle {
@@ -85,6 +98,8 @@ struct aw_handle {
   void* ddata = nullptr;         // the device DataTab (the model table's `data`)
   int data_groups = 0;           // aw_set_data: the AW_DATA_* groups the kernels write (0: off) into the caller's
                                  // buffers; nonzero selects the step kernels with stage_data
+  void* clone_scratch = nullptr; // aw_clone_envs: the gathered source rows (state and episode counters of nenv
+                                 // rows), allocated on the first call
 };
 
 // resident workgroups of a one-wave kernel on the device (occupancy x CUs): a persistent grid
@@ -117,6 +132,7 @@ struct TaskOps {
   void (*step)(aw_handle*, const float*, float*, float*, uint8_t*, uint8_t*, float*, int, uint64_t, hipStream_t);
   void (*reset)(aw_handle*, const uint8_t*, const float*, uint64_t, float*, hipStream_t);
   void (*set)(aw_handle*, const float*, const float*, const float*, const float*, float*, hipStream_t);
+  void (*set_ids)(aw_handle*, const SetIds&, float*, hipStream_t);
   void (*dump)(aw_handle*, int, const float*, float*, hipStream_t);
   void (*depth)(aw_handle*, const CamRec&, int, int, float*, hipStream_t);
   void (*rgb)(aw_handle*, const CamRec&, const LookRec&, int, int, int, uint8_t*, float*, hipStream_t);

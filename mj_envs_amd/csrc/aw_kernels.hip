@@ -1,6 +1,6 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
-// -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_dump, k_depth, k_rgb, k_views,
+// -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_set_state_ids, k_dump, k_depth, k_rgb, k_views,
 // k_labels, k_cloud, k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
 // k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
 // env-step both tiers run is aw_step.h.
@@ -273,6 +273,69 @@ __global__ void __launch_bounds__(64) k_set_state(DModel m, DState st, int n, co
     if (warm) s.warm[lane] = warm[(size_t)env * m.nv + lane];
   }
   if (params && lane < m.nparam) st.params[(size_t)env * m.nparam + lane] = params[(size_t)env * m.nparam + lane];
+  __threadfence_block();
+  wsync();
+  if (lane < m.nu) s.ctrl[lane] = 0.f;
+  stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+  float Mrow[NV];
+  Dof d;
+  forward<TASK>(m, s, lane, Mrow, d);
+  store_env<NV>(m, s, st, env, lane);
+  if (fast_overflow(m, s)) {
+    if (lane == 0) { st.status[env] = s.status & ~ST_OVF; st.status_acc[env] |= s.status & ~ST_OVF; }
+    defer_env(defer, env, DK_FORWARD, lane);
+    return;
+  }
+  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
+  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
+  if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
+  if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
+}
+
+// k_set_state for a subset (aw_set_state_ids, aw_clone_envs): workgroup k sets env env_ids[k] from
+// row rows[k] (rows == nullptr: row row0 + k) of the non-null inputs and runs k_set_state's forward
+// for it -- the same statements in the same order, so a selected env ends bit for bit where
+// k_set_state would leave it.  env and row are wave-uniform scalars (readfirstlane, as claim_env's
+// result is): the addresses formed from them stay in SGPRs.  A pair whose env is outside [0, n),
+// whose row is outside [0, n_rows) or (also_ids != nullptr: aw_clone_envs' source ids) whose
+// also_ids[k] is outside [0, n) returns before it has written anything.  reset_episode zeroes the
+// env's running-episode counters as reset_prepare does; ep_len_in / ep_ret_in / ep_goal_in
+// (aw_clone_envs with episode != 0) replace them by row `row` of those arrays.  The finished-episode
+// count, the last-episode stats and the totals are never written.  The grid is at most n workgroups
+// (launch_set_ids): s.slot = blockIdx.x stays inside the per-env spill blocks and the deferred envs
+// inside the wide queue.
+template <int TASK>
+__global__ void __launch_bounds__(64) k_set_state_ids(DModel m, DState st, int n, const int* __restrict__ env_ids,
+                                                      const int* __restrict__ rows, const int* __restrict__ also_ids,
+                                                      int row0, int n_rows, const float* qpos, const float* qvel,
+                                                      const float* warm, const float* params, const int* ep_len_in,
+                                                      const float* ep_ret_in, const int* ep_goal_in, int reset_episode,
+                                                      float* obs, int* defer) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  const int lane = threadIdx.x;
+  const int env = __builtin_amdgcn_readfirstlane(env_ids[blockIdx.x]);
+  const int row = rows ? __builtin_amdgcn_readfirstlane(rows[blockIdx.x]) : row0 + (int)blockIdx.x;
+  if ((unsigned)env >= (unsigned)n || (unsigned)row >= (unsigned)n_rows) return;
+  if (also_ids && (unsigned)__builtin_amdgcn_readfirstlane(also_ids[blockIdx.x]) >= (unsigned)n) return;
+  load_env<NV>(m, s, st, env, lane);
+  if (lane < NV) {
+    if (qpos) s.qpos[lane] = qpos[(size_t)row * m.nq + lane];
+    if (qvel) s.qvel[lane] = qvel[(size_t)row * m.nv + lane];
+    if (warm) s.warm[lane] = warm[(size_t)row * m.nv + lane];
+  }
+  if (params && lane < m.nparam) st.params[(size_t)env * m.nparam + lane] = params[(size_t)row * m.nparam + lane];
+  if (lane == 0) {
+    if (ep_len_in) {
+      st.ep_len[env] = ep_len_in[row];
+      st.ep_ret[env] = ep_ret_in[row];
+      st.ep_goal[env] = ep_goal_in[row];
+    } else if (reset_episode) {
+      st.ep_len[env] = 0;
+      st.ep_ret[env] = 0.f;
+      st.ep_goal[env] = 0;
+    }
+  }
   __threadfence_block();
   wsync();
   if (lane < m.nu) s.ctrl[lane] = 0.f;
@@ -593,6 +656,20 @@ static void launch_set(aw_handle* h, const float* q, const float* v, const float
                      h->next_env + 8);
   wide_ops<TASK>()->run(h, nullptr, obs, nullptr, nullptr, nullptr, nullptr, 0, 0, st);
 }
+// one workgroup per selected pair, at most nenv per launch: a longer list (ids that repeat or lie
+// out of range) goes out in pieces, each with its own queue clear and wide-tier drain, so that
+// blockIdx.x indexes the per-env spill blocks and the queue never holds more than nenv entries
+template <int TASK>
+static void launch_set_ids(aw_handle* h, const SetIds& a, float* obs, hipStream_t st) {
+  for (int k0 = 0; k0 < a.n_sel; k0 += h->nenv) {
+    const int grid = std::min(h->nenv, a.n_sel - k0);
+    clear_queue(h, false, st);
+    hipLaunchKernelGGL((k_set_state_ids<TASK>), dim3(grid), dim3(64), 0, st, h->m, h->st, h->nenv, a.env_ids + k0,
+                       a.rows ? a.rows + k0 : nullptr, a.also_ids ? a.also_ids + k0 : nullptr, k0, a.n_rows, a.qpos,
+                       a.qvel, a.warm, a.params, a.ep_len, a.ep_ret, a.ep_goal, a.reset_episode, obs, h->next_env + 8);
+    wide_ops<TASK>()->run(h, nullptr, obs, nullptr, nullptr, nullptr, nullptr, 0, 0, st);
+  }
+}
 template <int TASK>
 static void launch_dump(aw_handle* h, int env, const float* ctrl, float* out, hipStream_t st) {
   hipLaunchKernelGGL((k_dump<TASK>), dim3(1), dim3(64), 0, st, h->m, h->st, env, ctrl, out);
@@ -649,7 +726,7 @@ static void launch_cloud(aw_handle* h, const ViewsRec& views, int nviews, const 
 }
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
-                              launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>,
+                              launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>, launch_set_ids<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
                               launch_labels<TASK>, launch_cloud<TASK>};
   return &ops;

@@ -338,17 +338,94 @@ class AdroitVecEnv:
         return out, count, index
 
     # --- state -----------------------------------------------------------------------------
-    def get_state(self) -> Dict[str, "object"]:
+    def _ids(self, ids, n: int, name: str, distinct: bool = True):
+        """ids as a device int32 vector: a host list / numpy array is checked (``_native.check_ids``:
+        integers in [0, n), distinct) and uploaded; a device int32 tensor passes through unread"""
+        import torch
+        if isinstance(ids, torch.Tensor) and ids.is_cuda:
+            if ids.dtype != torch.int32 or ids.dim() != 1:
+                raise ValueError(f"{name}: a device tensor of ids must be a one-dimensional int32 tensor")
+            return ids.contiguous()
+        if isinstance(ids, torch.Tensor):
+            ids = ids.numpy()
+        return torch.as_tensor(_native.check_ids(ids, n, name, distinct=distinct), device=self.sim.torch_device)
+
+    def get_state(self, env_ids=None) -> Dict[str, "object"]:
+        """qpos, qvel, qacc_warmstart and params of every env, or with ``env_ids`` (a list, a numpy
+        array or a device int32 tensor; ids may repeat) of those envs in that order: [len(ids), ...]"""
+        import torch
         s = self.sim
-        st = dict(qpos=s.empty(self.num_envs, self.nq), qvel=s.empty(self.num_envs, self.nv),
-                  qacc_warmstart=s.empty(self.num_envs, self.nv), params=s.empty(self.num_envs, self.nparam))
-        s.get_state(st["qpos"], st["qvel"], st["qacc_warmstart"], st["params"])
+        if env_ids is None:
+            st = dict(qpos=s.empty(self.num_envs, self.nq), qvel=s.empty(self.num_envs, self.nv),
+                      qacc_warmstart=s.empty(self.num_envs, self.nv), params=s.empty(self.num_envs, self.nparam))
+            s.get_state(st["qpos"], st["qvel"], st["qacc_warmstart"], st["params"])
+            return st
+        ids = self._ids(env_ids, self.num_envs, "env_ids", distinct=False)
+        n = int(ids.shape[0])
+        z = lambda w: torch.zeros(n, w, device=s.torch_device)   # (a row of an id out of range stays zero)
+        st = dict(qpos=z(self.nq), qvel=z(self.nv), qacc_warmstart=z(self.nv), params=z(self.nparam))
+        s.get_state_ids(ids, st["qpos"], st["qvel"], st["qacc_warmstart"], st["params"])
         return st
 
-    def set_state(self, qpos=None, qvel=None, qacc_warmstart=None, params=None):
-        self.sim.set_state(qpos, qvel, qacc_warmstart, params, obs=self.obs)
+    def set_state(self, qpos=None, qvel=None, qacc_warmstart=None, params=None, env_ids=None, rows=None,
+                  reset_episode: bool = False):
+        """Set the state and run the forward; ``obs`` (and sensordata) are refreshed in place.
+        ``env_ids`` None: every env from the [N, ...] arrays.  With ``env_ids`` (distinct; a list, a
+        numpy array or a device int32 tensor) only those envs: env ``env_ids[k]`` takes row ``rows[k]``
+        (None: row k; rows may repeat -- a broadcast) of the given [n_rows, ...] arrays, an array left
+        None keeps the env's values, and every other env, its obs row included, is untouched.
+        ``reset_episode``: the selected envs' running-episode counters restart at zero (a
+        demonstration-state reset); the finished-episode counts and totals are never changed."""
+        if env_ids is None:
+            if rows is not None or reset_episode:
+                raise ValueError("set_state: rows and reset_episode need env_ids")
+            self.sim.set_state(qpos, qvel, qacc_warmstart, params, obs=self.obs)
+            self._read_sensors()
+            return self.obs
+        given = [t for t in (qpos, qvel, qacc_warmstart, params) if t is not None]
+        ids = self._ids(env_ids, self.num_envs, "env_ids")
+        n_sel = int(ids.shape[0])
+        n_rows = int(given[0].shape[0]) if given else n_sel
+        for t, w, k in ((qpos, self.nq, "qpos"), (qvel, self.nv, "qvel"), (qacc_warmstart, self.nv, "qacc_warmstart"),
+                        (params, self.nparam, "params")):
+            if t is not None and tuple(t.shape) != (n_rows, w):
+                raise ValueError(f"set_state: {k} must be [{n_rows}, {w}], not {tuple(t.shape)}")
+        if rows is not None:
+            if not given:
+                raise ValueError("set_state: rows without a state array to take them from")
+            rows = self._ids(rows, n_rows, "rows", distinct=False)
+            if int(rows.shape[0]) != n_sel:
+                raise ValueError(f"set_state: {int(rows.shape[0])} rows for {n_sel} env ids")
+        elif n_rows < n_sel:
+            raise ValueError(f"set_state: {n_sel} env ids but only {n_rows} rows (pass rows to repeat them)")
+        c = lambda t: None if t is None else t.contiguous()
+        self.sim.set_state_ids(ids, rows=rows, n_rows=n_rows, qpos=c(qpos), qvel=c(qvel), warm=c(qacc_warmstart),
+                               params=c(params), reset_episode=reset_episode, obs=self.obs)
         self._read_sensors()
         return self.obs
+
+    def clone(self, src, dst, episode: bool = True):
+        """Env ``dst[k]`` becomes a copy of env ``src[k]``: state, params and (``episode``) the running
+        episode's counters, then its forward (obs, sensordata and data rows of the dst envs).  Every
+        source is read before any destination is written: ``clone([0, 1], [1, 0])`` swaps two envs,
+        ``clone([0, 0, 0], [1, 2, 3])`` branches one.  ``dst`` distinct; lists, numpy arrays or device
+        int32 tensors.  The first call allocates a scratch block on the device."""
+        s_ids = self._ids(src, self.num_envs, "src", distinct=False)
+        d_ids = self._ids(dst, self.num_envs, "dst")
+        if s_ids.shape != d_ids.shape:
+            raise ValueError(f"clone: {int(s_ids.shape[0])} sources for {int(d_ids.shape[0])} destinations")
+        self.sim.clone_envs(s_ids, d_ids, episode=episode, obs=self.obs)
+        self._read_sensors()
+        return self.obs
+
+    def get_episode(self):
+        """the running episode of every env: ep_len, ep_ret, ep_goal, and the finished-episode count"""
+        import torch
+        s = self.sim
+        out = dict(ep_len=s.empty(self.num_envs, dtype=torch.int32), ep_ret=s.empty(self.num_envs),
+                   ep_goal=s.empty(self.num_envs, dtype=torch.int32), episodes=s.empty(self.num_envs, dtype=torch.int32))
+        s.get_episode(out["ep_len"], out["ep_ret"], out["ep_goal"], out["episodes"])
+        return out
 
     def episode_stats(self):
         import torch
