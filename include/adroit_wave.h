@@ -301,8 +301,21 @@ int aw_render_depth(aw_handle* h, const float* cam, int width, int height, float
  * max(r.v,0)^(128*shin)) ], a = the geom's rgb (explicit rgba, else its material's; geoms are
  * opaque), f = attenuation * spot (positional lights with cutoff < 180: (-l.dir)^exponent inside
  * the cone, 0 outside).  Lights: the camera headlight (a point light at the camera, no cone, no
- * attenuation), then the model's <light>s (up to 4).  No shadows, reflections, fog, skybox or
- * textures (a textured material is drawn with its rgba).
+ * attenuation), then the model's <light>s (up to 4).  No reflections, fog, skybox or textures (a
+ * textured material is drawn with its rgba).
+ *   Shadows: off unless aw_set_appearance switches them on.  Then they are hard shadows from an
+ * any-hit ray.  For a sample whose ray crosses entry g (a geom or a site) at P with facing normal n, a
+ * shadow ray is cast for each light that is not the headlight, has castshadow != 0 (slot 21 of its
+ * record), n.l > 0 and f > 0: origin P + 1e-4 n, direction l, tested over 0 < t < dist - 1e-4 for a
+ * positional light and over every t > 0 for a directional one.  Occluders are the primitive geoms
+ * only (finite planes and g itself included); sites never occlude but are shaded with shadows.  If
+ * any occluder is crossed, f = 0 for that light: its diffuse and specular terms vanish, its ambient
+ * term stays.  No penumbra, no shadow map.  A bounding-sphere test against the segment comes before
+ * each exact test; the result is the exhaustive loop's.
+ *   Appearance: with per-env tables on the handle (aw_set_appearance) env e is shaded from its own
+ * colour and light records and its own look row in place of the model's records and the host look.
+ * With shadows or tables on, aw_render_rgb renders through aw_render_views' path with one
+ * world-frame view (the same frames, as stated there).
  *   Stand-in rule: the hand's visual geoms are meshes (absent offline); the primitive collision
  * proxy of a group hidden by default (>= 3) is drawn with the colour and material of the first
  * mesh geom of its body, if there is one.
@@ -347,6 +360,49 @@ int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, 
 typedef struct { float rec[AW_CAM_FLOATS]; int32_t body; } aw_view;
 int aw_render_views(aw_handle* h, const aw_view* views, int nviews, const float* env_cam, const float* look,
                     int width, int height, int ss, uint8_t* rgb, float* depth, void* stream);
+
+/* Per-env appearance and cast shadows of the colour frames (visual domain randomisation).  Off by
+ * default; while off, every render call launches the kernels and writes the frames it did before.
+ * The state lives on the handle: aw_render_rgb and aw_render_views (rgb != NULL) pick it up;
+ * aw_render_labels, aw_render_cloud, aw_render_depth and depth-only aw_render_views ignore it.
+ *   app: NULL = tables off, else three DEVICE arrays, each of which may be NULL on its own.  Entry
+ * order is aw_render_entries': primitive geoms, then visible sites (ne = ngeom + nsite).  The caller
+ * owns the buffers; they must stay valid until appearance is switched off or the handle destroyed.
+ * The render kernels read them at launch: a write between two renders shows in the next frame.
+ * Tint rows apply on top of the per-env colour record as they do on top of the model's (hammer
+ * variation "mass" keeps its red channel).  look[e][0..2] is env e's background, 3..5 its headlight's
+ * ambient / diffuse / specular, 6 switches its headlight on.  Per-env records are not validated:
+ * whatever they hold, a workgroup writes only its own env's frames.
+ *   Light slot 21, castshadow: 1 in every model light record that aw_appearance_defaults returns and
+ * that the kernels stage from the model when no light table is given (MuJoCo's default; the Adroit
+ * models do not set the attribute, and the model table itself does not carry it), 0 in the
+ * headlight's; read only when shadows are on.
+ *   shadows: 1 casts the shadow rays defined at aw_render_rgb.  aw_set_appearance waits for the device.
+ *   aw_appearance_defaults copies the model's records to HOST arrays col [ne][8] and light
+ * [nlight][24] (either may be NULL) and the light count to nlight (may be NULL).
+ *   aw_appearance_sample draws records on the device, one thread per float of the env's record vector
+ * [col | light | look], F = ne*8 + nlight*24 + 7 floats, between the HOST bounds lo and hi [F]: float
+ * i of env e is lo[i] + (hi[i] - lo[i]) * u01(x), x = word i & 3 of philox({env_offset + e,
+ * (uint32)draw, 0xA99E, i >> 2}, seed) -- shards reproduce an unsharded run.  Flag slots are copied
+ * from lo: light 18 (cos cutoff), 20 (directional), 21 (castshadow) and look 6; a light's dir is
+ * renormalised after the draw.  env_ids: NULL = every env, else a DEVICE int32 array of n_sel ids --
+ * only those rows are written, an id outside [0, N) is skipped.  col / light / look: DEVICE outputs
+ * of the shapes above; a NULL one is not written.
+ * AW_EUNSUPPORTED: the model table has no appearance arrays.  AW_EINVAL: shadows not 0 or 1; in
+ * aw_appearance_sample a NULL lo or hi, all three outputs NULL, n_sel < 1 with env_ids given, or
+ * lo > hi (or a NaN) in any slot.  After either error every other call still works. */
+#define AW_COL_FLOATS   8    /* rgb, alpha, specular, 128*shininess, emission, pad */
+#define AW_LIGHT_FLOATS 24   /* pos dir ambient diffuse specular attenuation, cos(cutoff) or -2, exponent,
+                                directional, castshadow (slot 21), pad */
+typedef struct {
+  const float* col;    /* DEVICE [N][ngeom+nsite][AW_COL_FLOATS]  or NULL = the model's */
+  const float* light;  /* DEVICE [N][nlight][AW_LIGHT_FLOATS]     or NULL = the model's */
+  const float* look;   /* DEVICE [N][AW_LOOK_FLOATS]              or NULL = the call's host look */
+} aw_appearance;
+int aw_set_appearance(aw_handle* h, const aw_appearance* app, int shadows);
+int aw_appearance_defaults(const aw_handle* h, float* col, float* light, int* nlight);
+int aw_appearance_sample(aw_handle* h, const float* lo, const float* hi, const int32_t* env_ids, int n_sel,
+                         uint64_t seed, uint64_t draw, float* col, float* light, float* look, void* stream);
 
 /* Segmentation frames: what each pixel of a camera shows (mujoco-py's sim.render(...,
  * segmentation=True)).  The ray caster's render entries are the primitive (non-mesh) geoms in model

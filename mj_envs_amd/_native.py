@@ -78,6 +78,17 @@ class View(ctypes.Structure):
     _fields_ = [("rec", ctypes.c_float * 17), ("body", ctypes.c_int32)]
 
 
+class AppearanceBufs(ctypes.Structure):
+    """aw_appearance (include/adroit_wave.h): the per-env colour, light and look tables, device pointers"""
+    _fields_ = [("col", _vp), ("light", _vp), ("look", _vp)]
+
+
+AW_COL_FLOATS, AW_LIGHT_FLOATS, AW_LOOK_FLOATS = 8, 24, 7
+# slots of a record vector [col | light | look] that aw_appearance_sample copies from ``lo``
+LIGHT_FLAG_SLOTS = (18, 20, 21)
+LOOK_FLAG_SLOT = 6
+
+
 def data_groups(data) -> int:
     """AW_DATA_* mask of ``data``: False / None -> 0, True -> every group, a group name or an
     iterable of them ("kin", "dyn", "contact"), or the mask itself"""
@@ -175,6 +186,13 @@ def load():
         L.aw_render_cloud.restype = ctypes.c_int
         L.aw_cloud_fps.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]
         L.aw_cloud_fps.restype = ctypes.c_int
+    if hasattr(L, "aw_set_appearance"):
+        L.aw_set_appearance.argtypes = [_vp, ctypes.POINTER(AppearanceBufs), ctypes.c_int]
+        L.aw_appearance_defaults.argtypes = [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_int)]
+        L.aw_appearance_sample.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                           _vp, _vp, _vp, _vp]
+        for f in ("aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample"):
+            getattr(L, f).restype = ctypes.c_int
     if hasattr(L, "aw_set_state_ids"):
         L.aw_set_state_ids.argtypes = [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
                                        _vp, _vp]
@@ -203,7 +221,7 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_set_episode",
            "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_render_rgb",
            "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_render_cloud", "aw_cloud_fps",
-           "aw_policy_mlp",
+           "aw_policy_mlp", "aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample",
            "aw_collide_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
@@ -592,6 +610,59 @@ class Sim:
             assert lk.size == 7, "render_views: look record has 7 floats"
         _check(load().aw_render_views(self.h, arr, nv, _ptr(env_cam), None if lk is None else lk.ctypes.data, w, h,
                                       int(ss), _ptr(rgb), _ptr(depth), _stream()))
+
+    def set_appearance(self, colors=None, lights=None, look=None, shadows: bool = False):
+        """Per-env appearance tables and cast shadows of the colour frames (include/adroit_wave.h
+        aw_set_appearance).  colors [n_envs, ne, 8], lights [n_envs, nlight, 24], look [n_envs, 7]:
+        contiguous fp32 device tensors or None (the model's records / the call's host look); the
+        handle keeps references, so they stay alive until they are replaced.  All None and
+        ``shadows`` False: everything off.  Waits for the device."""
+        import torch
+        ng, ns = self.render_entries()
+        for t, shape, name in ((colors, (self.n_envs, ng + ns, AW_COL_FLOATS), "colors"),
+                               (lights, (self.n_envs, self.appearance_defaults()[1].shape[0], AW_LIGHT_FLOATS), "lights"),
+                               (look, (self.n_envs, AW_LOOK_FLOATS), "look")):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                                 tuple(t.shape) == shape), f"set_appearance: {name} must be device fp32 {shape}"
+        bufs = None
+        if colors is not None or lights is not None or look is not None:
+            bufs = AppearanceBufs(_ptr(colors), _ptr(lights), _ptr(look))
+        _check(load().aw_set_appearance(self.h, None if bufs is None else ctypes.byref(bufs), int(shadows)))
+        self._appearance = (colors, lights, look)
+
+    def appearance_defaults(self):
+        """(colors [ne, 8], lights [nlight, 24]): the model's own records as host fp32 arrays
+        (include/adroit_wave.h aw_appearance_defaults)"""
+        nl = ctypes.c_int()
+        _check(load().aw_appearance_defaults(self.h, None, None, ctypes.byref(nl)))
+        col = np.zeros((sum(self.render_entries()), AW_COL_FLOATS), np.float32)
+        light = np.zeros((nl.value, AW_LIGHT_FLOATS), np.float32)
+        _check(load().aw_appearance_defaults(self.h, col.ctypes.data, light.ctypes.data, None))
+        return col, light
+
+    def appearance_sample(self, lo, hi, colors=None, lights=None, look=None, env_ids=None, seed: int = 0,
+                          draw: int = 0, n_sel: Optional[int] = None):
+        """Draw per-env appearance records on the device between the host bounds ``lo`` / ``hi``
+        (record vectors [col | light | look]; include/adroit_wave.h aw_appearance_sample) into the
+        given device tensors (None: not written).  env_ids: a device int32 vector, only those rows
+        are written (None: every env)."""
+        import torch
+        lo = np.ascontiguousarray(lo, np.float32).ravel()
+        hi = np.ascontiguousarray(hi, np.float32).ravel()
+        ng, ns = self.render_entries()
+        nf = (ng + ns) * AW_COL_FLOATS + AW_LOOK_FLOATS
+        nf += AW_LIGHT_FLOATS * (lights.shape[1] if lights is not None else self.appearance_defaults()[1].shape[0])
+        assert lo.size == nf and hi.size == nf, f"appearance_sample: lo and hi hold {nf} floats"
+        n = 0
+        if env_ids is not None:
+            assert env_ids.is_cuda and env_ids.dtype == torch.int32 and env_ids.is_contiguous() and env_ids.dim() == 1, \
+                "appearance_sample: env_ids must be a device int32 vector"
+            n = env_ids.numel() if n_sel is None else int(n_sel)
+        for t in (colors, lights, look):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                                 t.shape[0] == self.n_envs), "appearance_sample: outputs are device fp32 [n_envs, ...]"
+        _check(load().aw_appearance_sample(self.h, lo.ctypes.data, hi.ctypes.data, _ptr(env_ids), n, int(seed), int(draw),
+                                           _ptr(colors), _ptr(lights), _ptr(look), _stream()))
 
     def render_entries(self):
         """(ngeom, nsite) of the ray caster's render entries: the primitive geoms in model order, then

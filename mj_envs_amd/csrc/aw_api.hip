@@ -129,6 +129,47 @@ __global__ void k_random_actions(int n, int nu, uint64_t seed, uint64_t step, ui
   }
 }
 
+// Appearance sampler (aw_appearance_sample): one thread per float of one env's record vector
+// [col | light | look] (F = nc + nl + AW_LOOK_FLOATS floats; row0 + blockIdx.y: the row).  Float i is
+// lo[i] + (hi[i] - lo[i]) u01(x), x = word i & 3 of philox({genv, draw, 0xA99E, i >> 2}, seed).  The
+// flag slots (light 18, 20, 21; look 6) are lo's.  A light's dir is renormalised: the thread of
+// a dir slot draws all three components and divides its own by their length, in fp64 (correctly
+// rounded whatever the fp32 divide / sqrt flags are, so the host restates it bit for bit); a zero
+// vector stays.  env_ids (nullptr: row r is env r): an id outside [0, n) is skipped; a null output
+// is not written.  Every store index is the env's own row.
+AW_DEV float appearance_draw(const float* lo, const float* hi, int i, uint32_t genv, uint64_t seed, uint64_t draw) {
+  uint32_t c[4] = {genv, (uint32_t)draw, 0xA99Eu, (uint32_t)(i >> 2)};
+  philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return lo[i] + (hi[i] - lo[i]) * u01(c[i & 3]);
+}
+__global__ void __launch_bounds__(256) k_appearance(int n, int nc, int nl, const float* __restrict__ lo,
+                                                    const float* __restrict__ hi, const int* __restrict__ env_ids,
+                                                    int row0, uint64_t env_offset, uint64_t seed, uint64_t draw, float* col,
+                                                    float* light, float* look) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, F = nc + nl + AW_LOOK_FLOATS;
+  const int row = row0 + (int)blockIdx.y;
+  const int env = env_ids ? env_ids[row] : row;
+  if (i >= F || (unsigned)env >= (unsigned)n) return;
+  const uint32_t genv = (uint32_t)(env_offset + (uint64_t)env);
+  float v = appearance_draw(lo, hi, i, genv, seed, draw);
+  if (i < nc) {
+    if (col) col[(size_t)env * nc + i] = v;
+  } else if (i < nc + nl) {
+    const int k = (i - nc) % LIGHT_W;
+    if (k == 18 || k == 20 || k == 21) v = lo[i];
+    if (k >= 3 && k < 6) {
+      const int i0 = i - (k - 3);
+      double d[3], nn = 0.0;
+      for (int q = 0; q < 3; q++) { d[q] = (double)appearance_draw(lo, hi, i0 + q, genv, seed, draw); nn += d[q] * d[q]; }
+      if (nn > 0.0) v = (float)(d[k - 3] / sqrt(nn));
+    }
+    if (light) light[(size_t)env * nl + (i - nc)] = v;
+  } else {
+    if (i - nc - nl == 6) v = lo[i];
+    if (look) look[(size_t)env * AW_LOOK_FLOATS + (i - nc - nl)] = v;
+  }
+}
+
 // The state rows of selected envs (aw_get_state_ids; aw_clone_envs' read pass): one wave per output
 // row, four per workgroup; row k receives env env_ids[k], an id outside [0, n) leaves it untouched.
 // The id is wave-uniform (readfirstlane), so the row bases are scalar.  Any output may be null; the
@@ -325,6 +366,7 @@ static void free_handle(aw_handle* h) {
   if (h->ddata) (void)hipFree(h->ddata);
   if (h->sensordata) (void)hipFree(h->sensordata);
   if (h->clone_scratch) (void)hipFree(h->clone_scratch);
+  if (h->app_bounds) (void)hipFree(h->app_bounds);
   delete h;
 }
 
@@ -749,7 +791,13 @@ int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, 
   memcpy(c.c, cam, sizeof(c.c));
   LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
   if (look) memcpy(l.c, look, sizeof(l.c));
-  h->ops->rgb(h, c, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  if (h->app.col || h->app.light || h->app.look || h->shadows) {   // one world-frame view: the same frames
+    ViewsRec r = {};
+    memcpy(r.c[0], cam, sizeof(r.c[0]));
+    h->ops->views_app(h, r, 1, nullptr, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  } else {
+    h->ops->rgb(h, c, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  }
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -772,7 +820,71 @@ int aw_render_views(aw_handle* h, const aw_view* views, int nviews, const float*
   }
   LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
   if (look) memcpy(l.c, look, sizeof(l.c));
-  h->ops->views(h, r, nviews, env_cam, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  if (rgb && (h->app.col || h->app.light || h->app.look || h->shadows))
+    h->ops->views_app(h, r, nviews, env_cam, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  else
+    h->ops->views(h, r, nviews, env_cam, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_set_appearance(aw_handle* h, const aw_appearance* app, int shadows) {
+  if (!h || (shadows != 0 && shadows != 1)) return fail(AW_EINVAL, "aw_set_appearance: shadows must be 0 or 1");
+  if (!h->m.appearance)
+    return fail(AW_EUNSUPPORTED, "aw_set_appearance: the model table carries no appearance arrays");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // frames already queued are shaded from the tables they were launched with
+  h->app = app ? AppRec{app->col, app->light, app->look} : AppRec{nullptr, nullptr, nullptr};
+  h->shadows = shadows;
+  return AW_OK;
+}
+
+int aw_appearance_defaults(const aw_handle* h, float* col, float* light, int* nlight) {
+  if (!h) return fail(AW_EINVAL, "aw_appearance_defaults: null");
+  if (!h->m.appearance)
+    return fail(AW_EUNSUPPORTED, "aw_appearance_defaults: the model table carries no appearance arrays");
+  HIPCHK(hipSetDevice(h->device));
+  const MData* d = (const MData*)h->dmodel;
+  const size_t ne = (size_t)(h->m.nrgeom + h->m.nrsite);
+  if (col) HIPCHK(hipMemcpy(col, d->rg_col, ne * COL_W * sizeof(float), hipMemcpyDeviceToHost));
+  if (light && h->m.nlight) {
+    HIPCHK(hipMemcpy(light, d->light, (size_t)h->m.nlight * LIGHT_W * sizeof(float), hipMemcpyDeviceToHost));
+    for (int l = 0; l < h->m.nlight; l++) light[l * LIGHT_W + 21] = 1.f;   // castshadow: MuJoCo's default
+  }
+  if (nlight) *nlight = h->m.nlight;
+  return AW_OK;
+}
+
+int aw_appearance_sample(aw_handle* h, const float* lo, const float* hi, const int32_t* env_ids, int n_sel,
+                         uint64_t seed, uint64_t draw, float* col, float* light, float* look, void* stream) {
+  if (!h) return fail(AW_EINVAL, "aw_appearance_sample: null");
+  if (!h->m.appearance)
+    return fail(AW_EUNSUPPORTED, "aw_appearance_sample: the model table carries no appearance arrays");
+  if (!lo || !hi || (!col && !light && !look) || (env_ids && n_sel < 1))
+    return fail(AW_EINVAL, "aw_appearance_sample: lo and hi, an output, and n_sel >= 1 with env_ids must be given");
+  const int nc = (h->m.nrgeom + h->m.nrsite) * COL_W, nl = h->m.nlight * LIGHT_W, F = nc + nl + AW_LOOK_FLOATS;
+  for (int i = 0; i < F; i++)
+    if (!(lo[i] <= hi[i])) return fail(AW_EINVAL, "aw_appearance_sample: the bounds need lo <= hi in every slot");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  // the bounds travel through a device block of the handle (too long for kernel arguments), uploaded
+  // only when they differ from the last call's: then the stream is drained first (a sampler launch
+  // still queued reads the old bounds) and the copy is complete before the host arrays are let go
+  const size_t cap = (size_t)(MAXRG * COL_W + MAXLIGHT * LIGHT_W + AW_LOOK_FLOATS);
+  if (!h->app_bounds) HIPCHK(hipMalloc((void**)&h->app_bounds, 2 * cap * sizeof(float)));
+  std::vector<float> b(lo, lo + F);
+  b.insert(b.end(), hi, hi + F);
+  if (b.size() != h->app_bounds_host.size() || memcmp(b.data(), h->app_bounds_host.data(), b.size() * sizeof(float))) {
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(h->app_bounds, lo, F * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->app_bounds + cap, hi, F * sizeof(float), hipMemcpyHostToDevice));
+    h->app_bounds_host.swap(b);
+  }
+  const int rows = env_ids ? n_sel : h->nenv;
+  for (int r0 = 0; r0 < rows; r0 += 65535)   // the grid's y limit
+    hipLaunchKernelGGL(k_appearance, dim3((F + 255) / 256, std::min(rows - r0, 65535)), dim3(256), 0, st, h->nenv, nc, nl,
+                       h->app_bounds, h->app_bounds + cap, env_ids, r0, (uint64_t)h->m.env_offset, seed, draw, col,
+                       light, look);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }

@@ -208,7 +208,7 @@ constexpr int MAXTIDX = 16;   // task object ids
 constexpr int MAXRG = 64;     // render table: primitive geoms + visible sites (one ballot)
 constexpr int MAXTINT = 4;    // tint rows of the task block
 constexpr int MAXLIGHT = 4;   // model lights (the colour renderer adds the camera headlight)
-constexpr int LIGHT_W = 24;   // light record: pos dir ambient diffuse specular attenuation, cos(cutoff) or -2, exponent, directional
+constexpr int LIGHT_W = 24;   // light record: pos dir ambient diffuse specular attenuation, cos(cutoff) or -2, exponent, directional, castshadow (slot 21)
 constexpr int COL_W = 8;      // colour record: rgb alpha specular 128*shininess emission
 
 #define AW_MODEL_ARRAYS(X)                                                                     \

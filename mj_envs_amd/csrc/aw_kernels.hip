@@ -460,6 +460,75 @@ __global__ void __launch_bounds__(256) k_views(DModel m, DState st, int n, Views
   }
 }
 
+// k_views<TASK, true> with the handle's appearance state (aw_set_appearance), in instantiations of
+// its own so that k_views stays the kernel it was.  APP: env e's colour and light records come from
+// app.col + e ne COL_W / app.light + e nlight LIGHT_W and its look from app.look + e AW_LOOK_FLOATS,
+// each where the pointer is given (nullptr: the model's records / the launch's host look).  The look
+// row goes through LDS into scalar registers once per block, as the camera record does.  SHADOW:
+// shade casts the shadow rays (aw_render.h occluded) against the candidates of the lights' occluder
+// grids (RShadow: 10 KiB of LDS, built per view behind two more uniform barriers).  waves_per_eu(4):
+// left alone the shadow instantiations take 142 VGPRs, three waves per SIMD; capped at 128 (48 bytes
+// of scratch) they run four, which is what 39.7 KiB of LDS allows anyway -- 2.68 -> 2.20 ms per
+// 64x64 frame of 8 192 hammer envs.  The instantiations without shadows take 91 and are not affected.  Whatever the per-env records hold, every
+// output index is blockIdx.x, the view and the lane: a workgroup writes only its own env's frames.
+template <int TASK, bool APP, bool SHADOW>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_views_app(DModel m, DState st, int n, ViewsRec views, int nviews,
+                                                   const float* __restrict__ env_cam, LookRec look, AppRec app, int W,
+                                                   int H, int ss, unsigned char* out, int dwords, float* depth) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RGeoms rg;
+  __shared__ RColors rc;
+  __shared__ float lcam[AW_CAM_FLOATS];
+  __shared__ float llook[AW_LOOK_FLOATS];
+  __shared__ std::conditional_t<SHADOW, RShadow, NoColors> sh;
+  const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (env >= n) return;
+  if (tid < 64) {
+    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+    wsync();
+    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+    stage_kinematics(m, s, lane);
+  } else if (tid < 64 + AW_LOOK_FLOATS) {
+    const int k = tid - 64;
+    llook[k] = APP && app.look ? app.look[(size_t)env * AW_LOOK_FLOATS + k] : look.c[k];
+  }
+  __syncthreads();
+  float lk[AW_LOOK_FLOATS];
+  for (int k = 0; k < AW_LOOK_FLOATS; k++)
+    lk[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, llook[k])));
+  const int ne = m.nrgeom + m.nrsite;
+  render_colors_env(m, s, rc, lk, tid, 256, APP && app.col ? app.col + (size_t)env * ne * COL_W : nullptr,
+                    APP && app.light ? app.light + (size_t)env * m.nlight * LIGHT_W : nullptr);
+  const size_t np = (size_t)W * H;
+  for (int v = 0; v < nviews; v++) {
+    const size_t frame = (size_t)env * nviews + v;
+    compose_view(s, env_cam ? env_cam + frame * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid);
+    __syncthreads();
+    float cam[AW_CAM_FLOATS];
+    for (int k = 0; k < AW_CAM_FLOATS; k++)
+      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    render_geoms(m, s, rg, cam, tid, 256);
+    render_sites(m, s, rg, cam, tid, 256);
+    render_headlight(rc, cam, lk, tid);
+    if (SHADOW && !(APP && app.light)) render_castshadow(m, rc, lk, tid);   // (behind the barrier above: the records are staged)
+    __syncthreads();
+    const RShadow* shp = nullptr;
+    if constexpr (SHADOW) {   // the lights' occluder grids over the poses render_geoms just wrote
+      shadow_frames(rg, rc, sh, m.nrgeom, tid);
+      __syncthreads();
+      shadow_cells(rg, rc, sh, m.nrgeom, tid, 256);
+      __syncthreads();
+      shp = &sh;
+    }
+    float* z = depth ? depth + frame * np : nullptr;
+    for (int p0 = (tid >> 6) * 64; p0 < W * H; p0 += 256)
+      render_span_rgb<SHADOW>(rg, rc, m.nrgeom, m.nrsite, cam, lk, W, H, ss, p0, lane, tid >> 6, out + frame * np * 3,
+                              dwords != 0, z, shp);
+    __syncthreads();   // the next view overwrites cam, the boxes and the headlight
+  }
+}
+
 // segmentation frames (aw_render_labels): k_views<TASK, false>'s structure -- the staging and the
 // kinematics once per env, per view compose_view, the pixel boxes and the 64-pixel spans -- writing
 // one int32 label per pixel (aw_render.h render_span_labels) and optionally the depth frame.
@@ -701,6 +770,20 @@ static void launch_views(aw_handle* h, const ViewsRec& views, int nviews, const 
   hipLaunchKernelGGL((k_views<TASK, true>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
                      env_cam, look, W, H, ss, rgb, dwords, depth);
 }
+// aw_render_views' RGB launch while the handle holds per-env tables and / or casts shadows
+template <int TASK>
+static void launch_views_app(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam,
+                             const LookRec& look, int W, int H, int ss, uint8_t* rgb, float* depth, hipStream_t st) {
+  const int dwords = (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;   // as launch_views
+  const bool app = h->app.col || h->app.light || h->app.look;
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews, env_cam, look,
+                       h->app, W, H, ss, rgb, dwords, depth);
+  };
+  if (app && h->shadows) go(k_views_app<TASK, true, true>);
+  else if (app) go(k_views_app<TASK, true, false>);
+  else go(k_views_app<TASK, false, true>);
+}
 // grid: the output rows (the selected envs, or all of them)
 template <int TASK>
 static void launch_labels(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam, const int32_t* env_ids,
@@ -728,7 +811,7 @@ template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>, launch_set_ids<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
-                              launch_labels<TASK>, launch_cloud<TASK>};
+                              launch_labels<TASK>, launch_cloud<TASK>, launch_views_app<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();

@@ -282,18 +282,29 @@ struct RColors {
 // the part of the per-env colour table that no camera enters: entry colours (tint rows: a colour
 // channel read from the env's params) and the model's lights, behind the headlight's slot
 // (look: background rgb, headlight ambient / diffuse / specular, headlight on)
-AW_DEV void render_colors_env(const DModel& m, const Env& s, RColors& c, const float* look, int tid, int nthreads) {
+// col / light (aw_set_appearance): this env's own records, [ne][COL_W] / [nlight][LIGHT_W] in device
+// memory, in place of the model's; nullptr: the model's.  The tint rows apply on top of either.
+AW_DEV void render_colors_env(const DModel& m, const Env& s, RColors& c, const float* look, int tid, int nthreads,
+                              const float* col = nullptr, const float* light = nullptr) {
   const int ne = m.nrgeom + m.nrsite;
   for (int i = tid; i < ne * COL_W; i += nthreads) {
     const int e = i / COL_W, k = i - e * COL_W;
-    float v = MD(rg_col, i);
+    float v = col ? col[i] : MD(rg_col, i);
     for (int t = 0; t < m.ntint; t++)
       if (MD(tint_entry, t) == e && MD(tint_chan, t) == k) v = s.prm[MD(tint_slot, t)] * MD(tint_scale, t);
     c.col[e][k] = v;
   }
   const int head = look[6] != 0.f ? 1 : 0;
-  for (int i = tid; i < m.nlight * LIGHT_W; i += nthreads) c.light[head + i / LIGHT_W][i % LIGHT_W] = MD(light, i);
+  for (int i = tid; i < m.nlight * LIGHT_W; i += nthreads)
+    c.light[head + i / LIGHT_W][i % LIGHT_W] = light ? light[i] : MD(light, i);
   if (tid == 0) c.nlight = head + m.nlight;
+}
+
+// castshadow of the model's own lights (behind the headlight's slot): slot 21 = 1, MuJoCo's default --
+// no Adroit XML sets the attribute, and the model table, whose bytes are pinned, does not carry it.
+// Only the kernels that cast shadows read the slot; a per-env light record brings its own.
+AW_DEV void render_castshadow(const DModel& m, RColors& c, const float* look, int tid) {
+  if (tid < m.nlight) c.light[(look[6] != 0.f ? 1 : 0) + tid][21] = 1.f;
 }
 
 // the headlight (light 0 when look switches it on): a point light at the camera, no cone, no
@@ -355,8 +366,186 @@ AW_DEV void prim_normal(int type, const float* size, const float* lp, float* n) 
 // x^e for shading exponents: 0 for x <= 0
 AW_DEV float shade_pow(float x, float e) { return x > 0.f ? exp2f(e * log2f(x)) : 0.f; }
 
-// linear rgb of entry g where the ray cam + t d crosses it
-AW_DEV void shade(const RGeoms& r, const RColors& c, int g, const float* cam, const float* d, float t, float* rgb) {
+// Cast shadows (aw_set_appearance, shadows 1): whether a primitive geom of `mask` -- entries [0, ng),
+// sites never occlude -- crosses the ray o + t l (l unit) at 0 < t < tmax.  Any hit ends the search.
+// Per occluder a conservative bounding-sphere test against the segment (the radius padded against
+// the rounding of the test itself; planes, rbound 0: none) comes before the exact crossing, so the
+// answer is the exhaustive loop's as long as mask holds every true occluder (RShadow below; all
+// ones: exhaustive).
+constexpr float SHADOW_EPS = 1.0e-4f;   // the origin's lift off the surface, and the segment's end before the light
+AW_DEV float shadow_rb(float rb) { return 1.001f * rb + 1.0e-6f; }
+AW_DEV bool occluded(const RGeoms& r, unsigned long long mask, const float* o, const float* l, float tmax) {
+  // The lanes' masks differ, but the loop is the wave's: each round takes the lowest candidate of
+  // the first lane that has one left (ballot + readlane: uniform among the lanes that are here,
+  // whatever branch they came through), and the lanes that hold it test it.  So every round works
+  // on one entry -- one primitive type, one broadcast LDS address -- instead of 64 different ones.
+  bool hit = false;
+  for (;;) {
+    const unsigned long long live = __ballot(mask != 0ull);
+    if (!live) break;
+    const int src = __builtin_ctzll(live);
+    const unsigned long long m = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)mask, src) |
+                                 (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(mask >> 32), src) << 32;
+    const int g = __builtin_ctzll(m);
+    const bool mine = ((mask >> g) & 1ull) != 0ull;
+    mask &= ~(1ull << g);
+    if (!mine) continue;
+    const float rb = r.rb[g];
+    if (rb > 0.f) {
+      float oc[3];
+      sub3(oc, r.pos[g], o);
+      const float tc = dot3(oc, l), rr = shadow_rb(rb);
+      if (dot3(oc, oc) - tc * tc > rr * rr || tc + rr < 0.f || tc - rr > tmax) continue;
+    }
+    const float t = ray_prim(r.pos[g], r.mat[g], r.size[g], r.type[g], o, l);
+    if (t > 0.f && t < tmax) { hit = true; mask = 0ull; }   // any hit ends this lane's search
+  }
+  return hit;
+}
+
+// The occluders that can lie between a point and a positional light, looked up instead of searched:
+// per casting light a SHADOW_GRID x SHADOW_GRID grid over the light's view of the scene (gnomonic
+// coordinates x = u.e1 / u.m0, y = u.e2 / u.m0 of a direction u from the light, |x|, |y| < T, about
+// the axis m0 towards the centroid of the occluders' centres), each cell holding the mask of the
+// occluders whose cone of directions from the light (axis: centre - light, half angle asin(rbound /
+// distance), the radius padded as in `occluded`) meets the cell's bounding cone.  A point's shadow
+// ray runs along the direction light -> point, so every geom it can cross is in the mask of that
+// direction's cell: a superset of the true occluders, and `occluded` makes the exact decision.
+// `always` holds what has no cone -- planes (rbound 0) and geoms that reach the light's own plane or
+// lie too far off the axis for the grid (tan > SHADOW_TMAX) -- and is part of every cell; a
+// direction off the grid can meet nothing else.  T is fitted to the gridded cones, so the cells are
+// as fine as the scene allows: a cell is about 15 cm across at the Adroit table.  Lights that do
+// not cast, directional lights and degenerate frames have on == 0: the exhaustive mask.
+// The poses are the env's and no camera enters, but the grid is rebuilt per view with the pixel
+// boxes (render_geoms fills the poses there); it costs a few microseconds per launch.
+constexpr int SHADOW_GRID = 16;
+constexpr float SHADOW_TMAX = 2.0f;
+struct RShadow {
+  unsigned long long cell[MAXLIGHT + 1][SHADOW_GRID * SHADOW_GRID];
+  unsigned long long always[MAXLIGHT + 1];
+  float fr[MAXLIGHT + 1][16];   // light pos, m0, e1, e2, T, cells per unit, on
+};
+
+// thread L < nlight: the frame and the extent of light L's grid
+AW_DEV void shadow_frames(const RGeoms& r, const RColors& c, RShadow& sh, int ng, int tid) {
+  if (tid >= c.nlight) return;
+  const float* q = c.light[tid];
+  float* f = sh.fr[tid];
+  f[14] = 0.f;
+  sh.always[tid] = ~0ull;
+  if (q[21] == 0.f || q[20] != 0.f) return;
+  float mean[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
+  for (int g = 0; g < ng; g++)
+    if (r.rb[g] > 0.f) { add3(mean, mean, r.pos[g]); cnt += 1.f; }
+  if (cnt == 0.f) return;
+  float m0[3], e1[3], e2[3];
+  for (int k = 0; k < 3; k++) m0[k] = mean[k] / cnt - q[k];
+  if (!(normalize3(m0) > 1.0e-6f)) return;
+  const float ax[3] = {fabsf(m0[0]) < 0.6f ? 1.f : 0.f, fabsf(m0[0]) < 0.6f ? 0.f : 1.f, 0.f};
+  cross3(e1, m0, ax);
+  normalize3(e1);
+  cross3(e2, m0, e1);
+  unsigned long long always = 0ull;
+  float T = 0.f;
+  for (int g = 0; g < ng; g++) {
+    const float rr = shadow_rb(r.rb[g]);
+    float a[3];
+    sub3(a, r.pos[g], q);
+    const float z = dot3(a, m0), D = norm3(a);
+    float tn = 3.0e38f;                                   // tan(angle off the axis + the cone's half angle)
+    if (r.rb[g] > 0.f && z > rr) {
+      const float ca = z / D, sn = rr / D;
+      const float ta = sqrtf(fmaxf(1.f - ca * ca, 0.f)) / ca, tt = sn / sqrtf(fmaxf(1.f - sn * sn, 1.0e-12f));
+      if (1.f - ta * tt > 0.05f) tn = (ta + tt) / (1.f - ta * tt);
+    }
+    if (tn < SHADOW_TMAX) T = fmaxf(T, tn);
+    else always |= 1ull << g;
+  }
+  T = 1.001f * T + 1.0e-4f;
+  for (int k = 0; k < 3; k++) { f[k] = q[k]; f[3 + k] = m0[k]; f[6 + k] = e1[k]; f[9 + k] = e2[k]; }
+  f[12] = T;
+  f[13] = (float)SHADOW_GRID / (2.f * T);
+  sh.always[tid] = always;
+  f[14] = T < SHADOW_TMAX + 1.f ? 1.f : 0.f;              // (a NaN record: off)
+}
+
+// one thread per cell: the cell's mask for every light whose grid is on
+AW_DEV void shadow_cells(const RGeoms& r, const RColors& c, RShadow& sh, int ng, int tid0, int nthreads) {
+  for (int tid = tid0; tid < SHADOW_GRID * SHADOW_GRID; tid += nthreads)
+  for (int L = 0; L < c.nlight; L++) {
+    const float* f = sh.fr[L];
+    if (f[14] == 0.f) continue;
+    const float T = f[12], w = 2.f * T / (float)SHADOW_GRID;
+    const float x0 = -T + w * (float)(tid % SHADOW_GRID), y0 = -T + w * (float)(tid / SHADOW_GRID);
+    float cd[3], cphi = 1.f;
+    for (int k = 0; k < 3; k++) cd[k] = f[3 + k] + (x0 + 0.5f * w) * f[6 + k] + (y0 + 0.5f * w) * f[9 + k];
+    normalize3(cd);
+    for (int q = 0; q < 4; q++) {
+      float v[3];
+      for (int k = 0; k < 3; k++) v[k] = f[3 + k] + (x0 + (q & 1 ? w : 0.f)) * f[6 + k] + (y0 + (q & 2 ? w : 0.f)) * f[9 + k];
+      normalize3(v);
+      cphi = fminf(cphi, dot3(v, cd));
+    }
+    const float sphi = sqrtf(fmaxf(1.f - cphi * cphi, 0.f));
+    const unsigned long long always = sh.always[L];
+    unsigned long long mask = always;
+    for (int g = 0; g < ng; g++) {
+      if ((always >> g) & 1ull) continue;
+      float a[3];
+      sub3(a, r.pos[g], f);
+      const float D = norm3(a), sn = shadow_rb(r.rb[g]) / D;   // < 1: z > rr in shadow_frames
+      const float cs = sqrtf(fmaxf(1.f - sn * sn, 0.f));
+      if (dot3(a, cd) / D >= cs * cphi - sn * sphi - 1.0e-4f) mask |= 1ull << g;
+    }
+    sh.cell[L][tid] = mask;
+  }
+}
+
+// the candidate occluders of light L for a shadow ray that starts at o
+AW_DEV unsigned long long shadow_mask(const RShadow& sh, int L, const float* o) {
+  const float* f = sh.fr[L];
+  if (f[14] == 0.f) return ~0ull;
+  float u[3];
+  sub3(u, o, f);
+  const float z = dot3(u, f + 3), T = f[12];
+  if (z > 0.f) {
+    const float x = dot3(u, f + 6) / z, y = dot3(u, f + 9) / z;
+    if (fabsf(x) < T && fabsf(y) < T) {
+      const int ix = min(max((int)((x + T) * f[13]), 0), SHADOW_GRID - 1);
+      const int iy = min(max((int)((y + T) * f[13]), 0), SHADOW_GRID - 1);
+      return sh.cell[L][iy * SHADOW_GRID + ix];
+    }
+  }
+  return sh.always[L];
+}
+
+// the point where the ray cam + t d crosses entry g, evaluated as entry_near does: from an origin
+// moved along the ray to two bounding radii in front of the entry's centre, where the quadratic's
+// cancellation is about 1e-6 m instead of the 1e-4 m it has from a camera metres away -- which is
+// SHADOW_EPS, so a shadow ray started from the coarse point could begin inside the entry it leaves.
+// Falls back to the coarse point where the moved origin grazes past.
+AW_DEV void shadow_point(const RGeoms& r, int g, const float* cam, const float* d, float t, float* P) {
+  const float rb = r.rb[g];
+  float s = 0.f, tt = t;
+  if (rb > 0.f) {
+    float oc[3], o[3];
+    sub3(oc, r.pos[g], cam);
+    s = fmaxf(dot3(oc, d) - 2.f * rb, 0.f);
+    for (int k = 0; k < 3; k++) o[k] = cam[k] + s * d[k];
+    const float t2 = ray_prim(r.pos[g], r.mat[g], r.size[g], r.type[g], o, d);
+    if (t2 >= 0.f && fabsf(s + t2 - t) < 1.0e-3f) tt = t2; else s = 0.f;
+  }
+  for (int k = 0; k < 3; k++) P[k] = (cam[k] + s * d[k]) + tt * d[k];
+}
+
+// linear rgb of entry g where the ray cam + t d crosses it.  SHADOW: a light with castshadow set
+// (slot 21; the headlight's is 0) that faces the surface (n.l > 0) with f > 0 is hidden -- f = 0, its
+// ambient term stays -- where `occluded` finds a primitive geom (entries [0, ng)) between the point
+// lifted SHADOW_EPS along the facing normal and the light: a positional light up to SHADOW_EPS
+// before it, a directional one without end.  sh: the light's grid of candidate occluders.
+template <bool SHADOW = false>
+AW_DEV void shade(const RGeoms& r, const RColors& c, int g, const float* cam, const float* d, float t, float* rgb,
+                  int ng = 0, const RShadow* sh = nullptr) {
   float P[3], dif[3], lp[3], nl[3], n[3];
   for (int k = 0; k < 3; k++) P[k] = cam[k] + t * d[k];
   sub3(dif, P, r.pos[g]);
@@ -370,10 +559,12 @@ AW_DEV void shade(const RGeoms& r, const RColors& c, int g, const float* cam, co
   for (int L = 0; L < c.nlight; L++) {
     const float* q = c.light[L];
     float l[3], f = 1.f;
+    float tmax = 3.0e38f;
     if (q[20] != 0.f) scl3(l, q + 3, -1.f);
     else {
       sub3(l, q, P);
       const float dist = normalize3(l);
+      tmax = dist - SHADOW_EPS;
       f = 1.f / (q[15] + dist * (q[16] + dist * q[17]));
       if (q[18] > -1.5f) {
         const float cs = -dot3(l, q + 3);
@@ -381,6 +572,15 @@ AW_DEV void shade(const RGeoms& r, const RColors& c, int g, const float* cam, co
       }
     }
     const float ndl = dot3(n, l);
+    if constexpr (SHADOW) {
+      if (q[21] != 0.f && ndl > 0.f && f > 0.f) {
+        float Ps[3];
+        shadow_point(r, g, cam, d, t, Ps);
+        for (int k = 0; k < 3; k++) Ps[k] += SHADOW_EPS * n[k];
+        const unsigned long long geoms = ng < 64 ? (1ull << ng) - 1ull : ~0ull;
+        if (occluded(r, shadow_mask(*sh, L, Ps) & geoms, Ps, l, tmax)) f = 0.f;
+      }
+    }
     float sp = 0.f;
     if (ndl > 0.f) {
       float rv = 0.f;
@@ -395,9 +595,10 @@ AW_DEV void shade(const RGeoms& r, const RColors& c, int g, const float* cam, co
 // colour (and optionally z-depth) of the 64 pixels [p0, p0 + 64) handled by wave `wave`: per
 // sample ray the nearest opaque geom (render_span's search), shaded; the MAXSITEHIT nearest
 // site crossings in front of it blended over it back to front; ss x ss samples averaged
+template <bool SHADOW = false>
 AW_DEV void render_span_rgb(const RGeoms& r, RColors& c, int ng, int ns, const float* cam, const float* look, int W,
                             int H, int ss, int p0, int lane, int wave, unsigned char* out, bool dwords,
-                            float* depth) {
+                            float* depth, const RShadow* sh = nullptr) {
   const int np = W * H;
   const int p = p0 + lane;
   const unsigned long long all = span_entries(r, ng + ns, W, H, p0, lane);
@@ -414,7 +615,7 @@ AW_DEV void render_span_rgb(const RGeoms& r, RColors& c, int ng, int ns, const f
       int hit;
       const float best = nearest_hit(r, gmask, cam, d, fc, fr, hit);
       if (depth && p < np) depth[p] = best < 1.0e38f ? best * dot3(d, cam + 3) : cam[16];
-      if (hit >= 0) shade(r, c, hit, cam, d, best, rgb);
+      if (hit >= 0) shade<SHADOW>(r, c, hit, cam, d, best, rgb, ng, sh);
       else copy3(rgb, look);
       // the nearest site crossings in front of the opaque one, sorted by t (registers)
       float st[MAXSITEHIT];
@@ -436,7 +637,7 @@ AW_DEV void render_span_rgb(const RGeoms& r, RColors& c, int ng, int ns, const f
       for (int k = MAXSITEHIT - 1; k >= 0; k--)
         if (sg[k] >= 0) {
           float sc[3];
-          shade(r, c, sg[k], cam, d, st[k], sc);
+          shade<SHADOW>(r, c, sg[k], cam, d, st[k], sc, ng, sh);
           const float al = c.col[sg[k]][3];
           for (int q = 0; q < 3; q++) rgb[q] = al * sc[q] + (1.f - al) * rgb[q];
         }

@@ -250,6 +250,44 @@ class AdroitVecEnv:
         self.sim.render_rgb(out, self._cam, ss=ss, depth=depth_out)
         return out
 
+    # --- per-env appearance and cast shadows (mj_envs_amd/appearance.py) -----------------------
+    def appearance(self):
+        """The batch's per-env appearance tables (``appearance.Appearance``: ``colors``, ``lights``,
+        ``look`` device tensors), created on first use from the model's records.  They shade the
+        colour frames once ``set_appearance(env.appearance())`` has switched them on."""
+        if getattr(self, "_appearance", None) is None:
+            from .appearance import Appearance
+            self._appearance = Appearance(self)
+        return self._appearance
+
+    def set_appearance(self, app=None, shadows: bool = False):
+        """Shade the colour frames (``render_rgb``, ``render_views``, the pixel wrapper) of env e from
+        row e of ``app``'s tables (an ``appearance.Appearance``; None: the model's records for every
+        env, as before) and, with ``shadows``, cast hard shadows from the model's lights
+        (include/adroit_wave.h aw_set_appearance).  Depth, segmentation and point clouds do not
+        change.  The kernels read the tables at launch: later writes to them show in the next frame."""
+        if app is None:
+            self.sim.set_appearance(shadows=bool(shadows))
+        else:
+            self.sim.set_appearance(app.colors, app.lights, app.look, shadows=bool(shadows))
+        self._appearance_on, self._shadows = app, bool(shadows)
+
+    def randomize_appearance(self, ranges, env_ids=None, seed: int = 0, draw: int = 0):
+        """Draw new appearance records on the device for every env (or the envs of ``env_ids``, a
+        device int32 vector or a list) between ``ranges`` = (lo, hi) of ``appearance.ranges``, into
+        ``env.appearance()``'s tables, and switch them on if they are not yet (shadows stay as they
+        are).  The draw of env e depends only on (seed, draw, global env id): repeatable."""
+        import torch
+        lo, hi = ranges
+        app = self.appearance()
+        if env_ids is not None and not isinstance(env_ids, torch.Tensor):
+            env_ids = torch.as_tensor(np.asarray(env_ids, np.int32).ravel(), device=self.sim.torch_device)
+        if env_ids is None or env_ids.numel() > 0:
+            self.sim.appearance_sample(lo, hi, app.colors, app.lights, app.look, env_ids=env_ids, seed=seed, draw=draw)
+        if getattr(self, "_appearance_on", None) is not app:
+            self.set_appearance(app, shadows=getattr(self, "_shadows", False))
+        return app
+
     def render_segmentation(self, cameras=None, width: int = 64, height: int = 64, kind: str = "geom", lut=None,
                             background: int = -1, sites: bool = False, env_ids=None, depth: bool = False, out=None,
                             depth_out=None, env_cams=None):
@@ -589,11 +627,14 @@ class _AdroitEnv(_reference_base()):
         (headless_observer.py:34-52), float64 [H, W, 3] in 0..255 from the HIP ray caster's shading
         model (mj_envs_amd/render.py; parity-unpinned against the reference's OpenGL frame):
         64x64 with 2x2 rays per pixel when ``enable_resize`` (the reference's resized 128x128 crop),
-        else the 128x128 crop itself.  ``mode="segmentation"``: mujoco-py's [H, W, 2] (type, id) frame.
+        else the 128x128 crop itself; ``shadows=True`` / ``False`` switches cast shadows on or off from
+        this frame on (``AdroitVecEnv.set_appearance``).  ``mode="segmentation"``: mujoco-py's [H, W, 2] (type, id) frame.
         ``mode="pointcloud"``: the farthest-point-sampled cloud [num_points, 3] of the camera's depth
         pixels (``AdroitVecEnv.render_pointcloud``; its keywords pass through)."""
         if mode == "rgb":
             size, ss = (64, 2) if enable_resize else (128, 1)
+            if "shadows" in kwargs and bool(kwargs["shadows"]) != getattr(self.vec, "_shadows", False):
+                self.vec.set_appearance(getattr(self.vec, "_appearance_on", None), shadows=bool(kwargs["shadows"]))
             return self.vec.render_rgb(size, size, ss=ss, camera=camera)[0].cpu().numpy().astype(np.float64)
         if mode == "segmentation":
             # mujoco-py's sim.render(..., segmentation=True): [H, W, 2] int32, channel 0 the mjtObj type

@@ -38,7 +38,10 @@ Stand-in rule: a collision proxy in a group hidden by default (>= 3) is drawn in
 material of the first mesh geom of its body (the hand: ``MatViz``); geoms are opaque.  Tint rows
 of the task block show a per-env param as a colour: hammer's ``variation_type="mass"`` sets the
 head's red channel to ``mass / 2.5`` as the reference does (``hammer_v0.py:118``).  No textures
-(a textured material is drawn with its rgba), shadows, reflections, fog or skybox.  Like depth
+(a textured material is drawn with its rgba), reflections, fog or skybox; hard cast shadows from
+the model's lights and per-env colours, lights and backgrounds are off unless
+``AdroitVecEnv.set_appearance`` / ``randomize_appearance`` switch them on
+(``mj_envs_amd/appearance.py``, ``tests/appearance_checker.py``).  Like depth
 this is parity-unpinned against the reference's OpenGL frame; it is checked against an fp64 numpy
 restatement of the model above (``tests/rgb_checker.py``, ``tests/test_render_rgb.py``).
 

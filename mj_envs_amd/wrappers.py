@@ -90,6 +90,16 @@ class PixelObservationVecEnv:
         self.env_cams = rk.get("env_cams")
         if self.env_cams is not None and self.cameras is None:
             raise ValueError("render_kwargs['env_cams'] needs render_kwargs['camera']")
+        # mode "rgb": render_kwargs["appearance"] = (lo, hi) of appearance.ranges -- every env draws its own
+        # colours, lights and background at reset() and again whenever its episode ends;
+        # render_kwargs["shadows"]: cast shadows (AdroitVecEnv.set_appearance)
+        self.appearance, self.shadows = rk.get("appearance"), bool(rk.get("shadows", False))
+        if (self.appearance is not None or self.shadows) and self.mode != "rgb":
+            raise ValueError("render_kwargs['appearance'] / ['shadows'] need mode 'rgb'")
+        self.appearance_seed = int(rk.get("appearance_seed", 0))
+        self.steps = 0          # step() calls so far: the draw index of the appearance sampler
+        if self.appearance is not None or self.shadows:
+            env.set_appearance(env.appearance() if self.appearance is not None else None, shadows=self.shadows)
         self.action_repeat = int(action_repeat)
         self.max_episode_length = 200          # wrappers.py:39 (hard-coded there too)
         import torch
@@ -185,6 +195,8 @@ class PixelObservationVecEnv:
     def reset(self, **kw):
         self.timer.zero_()
         self.env.reset(**kw)
+        if self.appearance is not None:      # every env looks new
+            self.env.randomize_appearance(self.appearance, seed=self.appearance_seed, draw=self.steps)
         self._pixels_fresh = False
         return self._obs(), {}
 
@@ -212,6 +224,12 @@ class PixelObservationVecEnv:
             info["goal_achieved"] = self.env.goal.bool()
         ended = term | trunc
         self.timer.masked_fill_(ended, 0)       # the kernel auto-reset these envs
+        self.steps += 1
+        if self.appearance is not None:
+            # the envs whose episode ended start the next one with a new look; the others keep theirs
+            ids = ended.nonzero().flatten().int()
+            if ids.numel():
+                self.env.randomize_appearance(self.appearance, env_ids=ids, seed=self.appearance_seed, draw=self.steps)
         if self.host_tensors:
             reward, term, trunc = reward.cpu(), term.cpu(), trunc.cpu()
             info = {k: (v.cpu() if hasattr(v, "cpu") else v) for k, v in info.items()}
