@@ -347,6 +347,25 @@ static int copy_fields(std::initializer_list<CopyField> fields, void* stream) {
   return AW_OK;
 }
 
+// The views of one render launch (fn: the entry point, for the message): every body must be a body
+// of the model; the records are host arrays and travel as a kernel argument.
+static int fill_views(const aw_handle* h, const char* fn, const aw_view* views, int nviews, ViewsRec& r) {
+  r = {};
+  for (int v = 0; v < nviews; v++) {
+    if (views[v].body < 0 || views[v].body >= h->m.nbody)
+      return fail(AW_EINVAL, std::string(fn) + ": a view's body is not a body of the model");
+    memcpy(r.c[v], views[v].rec, sizeof(r.c[v]));
+    r.body[v] = views[v].body;
+  }
+  return AW_OK;
+}
+// the caller's look record, or the default one
+static LookRec look_rec(const float* look) {
+  LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
+  if (look) memcpy(l.c, look, sizeof(l.c));
+  return l;
+}
+
 extern "C" {
 
 const char* aw_last_error(void) { return g_err.c_str(); }
@@ -789,14 +808,12 @@ int aw_render_rgb(aw_handle* h, const float* cam, const float* look, int width, 
   HIPCHK(hipSetDevice(h->device));
   CamRec c;
   memcpy(c.c, cam, sizeof(c.c));
-  LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
-  if (look) memcpy(l.c, look, sizeof(l.c));
-  if (h->app.col || h->app.light || h->app.look || h->shadows) {   // one world-frame view: the same frames
+  if (has_appearance(h)) {   // one world-frame view: the same frames
     ViewsRec r = {};
     memcpy(r.c[0], cam, sizeof(r.c[0]));
-    h->ops->views_app(h, r, 1, nullptr, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+    h->ops->views(h, r, 1, nullptr, look_rec(look), width, height, ss, rgb, depth, (hipStream_t)stream);
   } else {
-    h->ops->rgb(h, c, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+    h->ops->rgb(h, c, look_rec(look), width, height, ss, rgb, depth, (hipStream_t)stream);
   }
   HIPCHK(hipGetLastError());
   return AW_OK;
@@ -807,23 +824,12 @@ int aw_render_views(aw_handle* h, const aw_view* views, int nviews, const float*
   if (!h || !views || nviews < 1 || nviews > AW_MAX_VIEWS || (!rgb && !depth) || width <= 0 || height <= 0 ||
       width > 1024 || height > 1024 || (ss != 1 && ss != 2) || (ss != 1 && (depth || !rgb)))
     return fail(AW_EINVAL, "aw_render_views: bad arguments");
-  for (int v = 0; v < nviews; v++)
-    if (views[v].body < 0 || views[v].body >= h->m.nbody)
-      return fail(AW_EINVAL, "aw_render_views: a view's body is not a body of the model");
+  ViewsRec r;
+  if (int rc = fill_views(h, "aw_render_views", views, nviews, r)) return rc;
   if (rgb && !h->m.appearance)
     return fail(AW_EUNSUPPORTED, "aw_render_views: the model table carries no appearance arrays");
   HIPCHK(hipSetDevice(h->device));
-  ViewsRec r = {};
-  for (int v = 0; v < nviews; v++) {
-    memcpy(r.c[v], views[v].rec, sizeof(r.c[v]));   // host array: the records travel as a kernel argument
-    r.body[v] = views[v].body;
-  }
-  LookRec l = {{0.f, 0.f, 0.f, 0.1f, 0.4f, 0.5f, 1.f}};
-  if (look) memcpy(l.c, look, sizeof(l.c));
-  if (rgb && (h->app.col || h->app.light || h->app.look || h->shadows))
-    h->ops->views_app(h, r, nviews, env_cam, l, width, height, ss, rgb, depth, (hipStream_t)stream);
-  else
-    h->ops->views(h, r, nviews, env_cam, l, width, height, ss, rgb, depth, (hipStream_t)stream);
+  h->ops->views(h, r, nviews, env_cam, look_rec(look), width, height, ss, rgb, depth, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }
@@ -902,20 +908,14 @@ int aw_render_labels(aw_handle* h, const aw_view* views, int nviews, const float
   if (!h || !views || nviews < 1 || nviews > AW_MAX_VIEWS || !labels || width <= 0 || height <= 0 || width > 1024 ||
       height > 1024 || (env_ids && n_sel < 1) || (sites != 0 && sites != 1))
     return fail(AW_EINVAL, "aw_render_labels: bad arguments");
-  for (int v = 0; v < nviews; v++)
-    if (views[v].body < 0 || views[v].body >= h->m.nbody)
-      return fail(AW_EINVAL, "aw_render_labels: a view's body is not a body of the model");
+  ViewsRec r;
+  if (int rc = fill_views(h, "aw_render_labels", views, nviews, r)) return rc;
   if (sites && !h->m.appearance)
     return fail(AW_EUNSUPPORTED, "aw_render_labels: the model table carries no appearance arrays (no visible sites)");
   HIPCHK(hipSetDevice(h->device));
-  ViewsRec r = {};
-  for (int v = 0; v < nviews; v++) {
-    memcpy(r.c[v], views[v].rec, sizeof(r.c[v]));   // host array: the records travel as a kernel argument
-    r.body[v] = views[v].body;
-  }
   const int ne = h->m.nrgeom + h->m.nrsite;
   LutRec l;
-  for (int e = 0; e < MAXRG; e++) l.v[e] = e < ne && lut ? lut[e] : e;   // and so does the table
+  for (int e = 0; e < MAXRG; e++) l.v[e] = e < ne && lut ? lut[e] : e;   // a kernel argument, as the views are
   h->ops->labels(h, r, nviews, env_cam, env_ids, env_ids ? n_sel : h->nenv, l, background, sites, width, height, labels,
                  depth, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
@@ -929,9 +929,8 @@ int aw_render_cloud(aw_handle* h, const aw_view* views, int nviews, const float*
       width > 1024 || height > 1024 || (env_ids && n_sel < 1) || (sites != 0 && sites != 1) || cap < 1 ||
       cap > AW_CLOUD_MAXCAND)
     return fail(AW_EINVAL, "aw_render_cloud: bad arguments");
-  for (int v = 0; v < nviews; v++)
-    if (views[v].body < 0 || views[v].body >= h->m.nbody)
-      return fail(AW_EINVAL, "aw_render_cloud: a view's body is not a body of the model");
+  ViewsRec r;
+  if (int rc = fill_views(h, "aw_render_cloud", views, nviews, r)) return rc;
   if (frame_body < 0 || frame_body >= h->m.nbody)
     return fail(AW_EINVAL, "aw_render_cloud: frame_body is not a body of the model");
   for (int k = 0; box && k < 3; k++)
@@ -939,15 +938,10 @@ int aw_render_cloud(aw_handle* h, const aw_view* views, int nviews, const float*
   if (sites && !h->m.appearance)
     return fail(AW_EUNSUPPORTED, "aw_render_cloud: the model table carries no appearance arrays (no visible sites)");
   HIPCHK(hipSetDevice(h->device));
-  ViewsRec r = {};
-  for (int v = 0; v < nviews; v++) {
-    memcpy(r.c[v], views[v].rec, sizeof(r.c[v]));   // host array: the records travel as a kernel argument
-    r.body[v] = views[v].body;
-  }
   CloudRec c = {};
   const int ne = h->m.nrgeom + h->m.nrsite;
   for (int e = 0; e < ne; e++)
-    if (!keep || keep[e]) c.keep |= 1ull << e;   // and so do the keep table and the box
+    if (!keep || keep[e]) c.keep |= 1ull << e;   // kernel arguments too: the keep table and the box
   if (box) memcpy(c.box, box, sizeof(c.box));
   c.crop = box ? 1 : 0;
   c.frame_body = frame_body;

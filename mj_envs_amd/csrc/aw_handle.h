@@ -53,6 +53,7 @@ struct CloudRec {
 // [N][ne][COL_W], [N][nlight][LIGHT_W], [N][AW_LOOK_FLOATS]; nullptr: the model's / the launch's look
 struct AppRec {
   const float *col, *light, *look;
+  bool any() const { return col || light || look; }
 };
 static_assert(AW_COL_FLOATS == COL_W && AW_LIGHT_FLOATS == LIGHT_W, "the appearance records are the kernels' own");
 static_assert(MAXRG <= 64, "CloudRec::keep holds one bit per render entry");
@@ -105,13 +106,15 @@ struct aw_handle {
   int data_groups = 0;           // aw_set_data: the AW_DATA_* groups the kernels write (0: off) into the caller's
                                  // buffers; nonzero selects the step kernels with stage_data
   AppRec app = {nullptr, nullptr, nullptr};   // aw_set_appearance: per-env colour / light / look tables (all
-  int shadows = 0;                            // nullptr: off) and cast shadows; either one routes RGB frames to
-                                              // k_views_app
+  int shadows = 0;                            // nullptr: off) and cast shadows (has_appearance below)
   float* app_bounds = nullptr;          // aw_appearance_sample: the device copy of lo | hi, and what it holds
   std::vector<float> app_bounds_host;
   void* clone_scratch = nullptr; // aw_clone_envs: the gathered source rows (state and episode counters of nenv
                                  // rows), allocated on the first call
 };
+
+// the handle holds appearance tables or casts shadows: its RGB frames come from k_views_app
+static inline bool has_appearance(const aw_handle* h) { return h->app.any() || h->shadows; }
 
 // resident workgroups of a one-wave kernel on the device (occupancy x CUs): a persistent grid
 template <class K>
@@ -153,8 +156,6 @@ struct TaskOps {
                  int, int32_t*, float*, hipStream_t);
   void (*cloud)(aw_handle*, const ViewsRec&, int, const float*, const int32_t*, int, const CloudRec&, int, int, int,
                 float*, int32_t*, int32_t*, hipStream_t);
-  void (*views_app)(aw_handle*, const ViewsRec&, int, const float*, const LookRec&, int, int, int, uint8_t*, float*,
-                    hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 

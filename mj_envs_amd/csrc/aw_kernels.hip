@@ -1,9 +1,10 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
 // -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_set_state_ids, k_dump, k_depth, k_rgb, k_views,
-// k_labels, k_cloud, k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide tier: k_step_wide,
-// k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
-// env-step both tiers run is aw_step.h.
+// k_views_app, k_labels, k_cloud, k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide
+// tier: k_step_wide, k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
+// env-step both tiers run is aw_step.h.  Written once: finish_forward (the tail of k_reset and the set-state kernels),
+// set_state_body (both set-state kernels), stage_pose / view_cam (the render kernels' prologue and per-view camera).
 #ifndef AW_TASK_TU
 #error "aw_kernels.hip is one task's unit: compile it with -DAW_TASK_TU=<task kind>"
 #endif
@@ -233,6 +234,27 @@ __global__ void __launch_bounds__(64) AW_KSTEP_ATTR k_step(DModel mval, const DM
   }
 }
 
+// The tail of every kernel that leaves an env in a new state (k_reset, k_set_state, k_set_state_ids):
+// the forward, the state stored, an env that overflows the fast capacities handed to the wide tier
+// (which finishes it), else the sensors, the mjData views, the obs row and the status.
+template <int TASK>
+AW_DEV void finish_forward(const DModel& m, Env& s, const DState& st, int env, int lane, float* obs, int* defer) {
+  constexpr int NV = Tree<TASK>::NV;
+  float Mrow[NV];
+  Dof d;
+  forward<TASK>(m, s, lane, Mrow, d);
+  store_env<NV>(m, s, st, env, lane);
+  if (fast_overflow(m, s)) {
+    if (lane == 0) { st.status[env] = s.status & ~ST_OVF; st.status_acc[env] |= s.status & ~ST_OVF; }
+    defer_env(defer, env, DK_FORWARD, lane);
+    return;
+  }
+  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
+  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
+  if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
+  if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
+}
+
 template <int TASK>
 __global__ void __launch_bounds__(64) k_reset(DModel m, DState st, int n, const uint8_t* mask,
                                               const float* params, uint64_t seed, float* obs, int* defer) {
@@ -243,81 +265,20 @@ __global__ void __launch_bounds__(64) k_reset(DModel m, DState st, int n, const 
   if (mask && !mask[env]) return;
   if (lane == 0) { s.status = 0u; s.slot = blockIdx.x; }
   reset_prepare<NV>(m, s, st, env, lane, params, seed);
-  float Mrow[NV];
-  Dof d;
-  forward<TASK>(m, s, lane, Mrow, d);
-  store_env<NV>(m, s, st, env, lane);
-  if (fast_overflow(m, s)) {
-    if (lane == 0) { st.status[env] = s.status & ~ST_OVF; st.status_acc[env] |= s.status & ~ST_OVF; }
-    defer_env(defer, env, DK_FORWARD, lane);
-    return;
-  }
-  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
-  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
-  if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
-  if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
+  finish_forward<TASK>(m, s, st, env, lane, obs, defer);
 }
 
+// Env `env` takes row `row` of the non-null inputs and runs the forward (k_set_state: env = row =
+// blockIdx.x; k_set_state_ids: a selected pair).  Both kernels run these statements in this order,
+// so a selected env ends bit for bit where k_set_state would leave it.  ep_len_in / ep_ret_in /
+// ep_goal_in (aw_clone_envs with episode != 0) replace the env's running-episode counters by row
+// `row` of those arrays; else reset_episode zeroes them as reset_prepare does.  The finished-episode
+// count, the last-episode stats and the totals are never written.
 template <int TASK>
-__global__ void __launch_bounds__(64) k_set_state(DModel m, DState st, int n, const float* qpos,
-                                                  const float* qvel, const float* warm,
-                                                  const float* params, float* obs, int* defer) {
+AW_DEV void set_state_body(const DModel& m, Env& s, const DState& st, int env, int row, int lane, const float* qpos,
+                           const float* qvel, const float* warm, const float* params, const int* ep_len_in,
+                           const float* ep_ret_in, const int* ep_goal_in, int reset_episode, float* obs, int* defer) {
   constexpr int NV = Tree<TASK>::NV;
-  __shared__ Env s;
-  const int env = blockIdx.x, lane = threadIdx.x;
-  if (env >= n) return;
-  load_env<NV>(m, s, st, env, lane);
-  if (lane < NV) {
-    if (qpos) s.qpos[lane] = qpos[(size_t)env * m.nq + lane];
-    if (qvel) s.qvel[lane] = qvel[(size_t)env * m.nv + lane];
-    if (warm) s.warm[lane] = warm[(size_t)env * m.nv + lane];
-  }
-  if (params && lane < m.nparam) st.params[(size_t)env * m.nparam + lane] = params[(size_t)env * m.nparam + lane];
-  __threadfence_block();
-  wsync();
-  if (lane < m.nu) s.ctrl[lane] = 0.f;
-  stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-  float Mrow[NV];
-  Dof d;
-  forward<TASK>(m, s, lane, Mrow, d);
-  store_env<NV>(m, s, st, env, lane);
-  if (fast_overflow(m, s)) {
-    if (lane == 0) { st.status[env] = s.status & ~ST_OVF; st.status_acc[env] |= s.status & ~ST_OVF; }
-    defer_env(defer, env, DK_FORWARD, lane);
-    return;
-  }
-  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
-  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
-  if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
-  if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
-}
-
-// k_set_state for a subset (aw_set_state_ids, aw_clone_envs): workgroup k sets env env_ids[k] from
-// row rows[k] (rows == nullptr: row row0 + k) of the non-null inputs and runs k_set_state's forward
-// for it -- the same statements in the same order, so a selected env ends bit for bit where
-// k_set_state would leave it.  env and row are wave-uniform scalars (readfirstlane, as claim_env's
-// result is): the addresses formed from them stay in SGPRs.  A pair whose env is outside [0, n),
-// whose row is outside [0, n_rows) or (also_ids != nullptr: aw_clone_envs' source ids) whose
-// also_ids[k] is outside [0, n) returns before it has written anything.  reset_episode zeroes the
-// env's running-episode counters as reset_prepare does; ep_len_in / ep_ret_in / ep_goal_in
-// (aw_clone_envs with episode != 0) replace them by row `row` of those arrays.  The finished-episode
-// count, the last-episode stats and the totals are never written.  The grid is at most n workgroups
-// (launch_set_ids): s.slot = blockIdx.x stays inside the per-env spill blocks and the deferred envs
-// inside the wide queue.
-template <int TASK>
-__global__ void __launch_bounds__(64) k_set_state_ids(DModel m, DState st, int n, const int* __restrict__ env_ids,
-                                                      const int* __restrict__ rows, const int* __restrict__ also_ids,
-                                                      int row0, int n_rows, const float* qpos, const float* qvel,
-                                                      const float* warm, const float* params, const int* ep_len_in,
-                                                      const float* ep_ret_in, const int* ep_goal_in, int reset_episode,
-                                                      float* obs, int* defer) {
-  constexpr int NV = Tree<TASK>::NV;
-  __shared__ Env s;
-  const int lane = threadIdx.x;
-  const int env = __builtin_amdgcn_readfirstlane(env_ids[blockIdx.x]);
-  const int row = rows ? __builtin_amdgcn_readfirstlane(rows[blockIdx.x]) : row0 + (int)blockIdx.x;
-  if ((unsigned)env >= (unsigned)n || (unsigned)row >= (unsigned)n_rows) return;
-  if (also_ids && (unsigned)__builtin_amdgcn_readfirstlane(also_ids[blockIdx.x]) >= (unsigned)n) return;
   load_env<NV>(m, s, st, env, lane);
   if (lane < NV) {
     if (qpos) s.qpos[lane] = qpos[(size_t)row * m.nq + lane];
@@ -326,33 +287,67 @@ __global__ void __launch_bounds__(64) k_set_state_ids(DModel m, DState st, int n
   }
   if (params && lane < m.nparam) st.params[(size_t)env * m.nparam + lane] = params[(size_t)row * m.nparam + lane];
   if (lane == 0) {
-    if (ep_len_in) {
-      st.ep_len[env] = ep_len_in[row];
-      st.ep_ret[env] = ep_ret_in[row];
-      st.ep_goal[env] = ep_goal_in[row];
-    } else if (reset_episode) {
-      st.ep_len[env] = 0;
-      st.ep_ret[env] = 0.f;
-      st.ep_goal[env] = 0;
-    }
+    if (ep_len_in) { st.ep_len[env] = ep_len_in[row]; st.ep_ret[env] = ep_ret_in[row]; st.ep_goal[env] = ep_goal_in[row]; }
+    else if (reset_episode) { st.ep_len[env] = 0; st.ep_ret[env] = 0.f; st.ep_goal[env] = 0; }
   }
   __threadfence_block();
   wsync();
   if (lane < m.nu) s.ctrl[lane] = 0.f;
   stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-  float Mrow[NV];
-  Dof d;
-  forward<TASK>(m, s, lane, Mrow, d);
-  store_env<NV>(m, s, st, env, lane);
-  if (fast_overflow(m, s)) {
-    if (lane == 0) { st.status[env] = s.status & ~ST_OVF; st.status_acc[env] |= s.status & ~ST_OVF; }
-    defer_env(defer, env, DK_FORWARD, lane);
-    return;
-  }
-  if (SENSTAB()->out) stage_sensors(m, s, lane, env);
-  if (DATATAB()->groups) stage_data(m, s, lane, env, d.qacc, d.qfrc_con);
-  if (obs) write_obs(m, s, lane, obs + (size_t)env * m.obs_dim);
-  if (lane == 0) { st.status[env] = s.status; st.status_acc[env] |= s.status; }
+  finish_forward<TASK>(m, s, st, env, lane, obs, defer);
+}
+
+// every env from its own row; reads no id array and leaves the episode counters alone
+template <int TASK>
+__global__ void __launch_bounds__(64) k_set_state(DModel m, DState st, int n, const float* qpos, const float* qvel,
+                                                  const float* warm, const float* params, float* obs, int* defer) {
+  __shared__ Env s;
+  const int env = blockIdx.x, lane = threadIdx.x;
+  if (env >= n) return;
+  set_state_body<TASK>(m, s, st, env, env, lane, qpos, qvel, warm, params, nullptr, nullptr, nullptr, 0, obs, defer);
+}
+
+// a subset (aw_set_state_ids, aw_clone_envs): workgroup k sets env env_ids[k] from row rows[k] (rows ==
+// nullptr: row row0 + k).  env and row are wave-uniform scalars (readfirstlane, as claim_env's
+// result is): the addresses formed from them stay in SGPRs.  A pair whose env is outside [0, n),
+// whose row is outside [0, n_rows) or (also_ids != nullptr: aw_clone_envs' source ids) whose
+// also_ids[k] is outside [0, n) returns before it has written anything.  The grid is at most n
+// workgroups (launch_set_ids): s.slot = blockIdx.x stays inside the per-env spill blocks and the
+// deferred envs inside the wide queue.
+template <int TASK>
+__global__ void __launch_bounds__(64) k_set_state_ids(DModel m, DState st, int n, const int* __restrict__ env_ids,
+                                                      const int* __restrict__ rows, const int* __restrict__ also_ids,
+                                                      int row0, int n_rows, const float* qpos, const float* qvel,
+                                                      const float* warm, const float* params, const int* ep_len_in,
+                                                      const float* ep_ret_in, const int* ep_goal_in, int reset_episode,
+                                                      float* obs, int* defer) {
+  __shared__ Env s;
+  const int lane = threadIdx.x;
+  const int env = __builtin_amdgcn_readfirstlane(env_ids[blockIdx.x]);
+  const int row = rows ? __builtin_amdgcn_readfirstlane(rows[blockIdx.x]) : row0 + (int)blockIdx.x;
+  if ((unsigned)env >= (unsigned)n || (unsigned)row >= (unsigned)n_rows) return;
+  if (also_ids && (unsigned)__builtin_amdgcn_readfirstlane(also_ids[blockIdx.x]) >= (unsigned)n) return;
+  set_state_body<TASK>(m, s, st, env, row, lane, qpos, qvel, warm, params, ep_len_in, ep_ret_in, ep_goal_in,
+                       reset_episode, obs, defer);
+}
+
+// What the render kernels share.  stage_pose: wave 0 brings env's pose into LDS (qpos, the model rows
+// of its params, the kinematics) before the block's first barrier.  view_cam: a view's world record
+// composed into LDS and, behind one barrier, held in scalar registers (it is uniform over the block, as
+// k_rgb's kernel argument is).  Every barrier of a view loop is uniform: nviews is a kernel argument
+// and an early return takes the whole block.
+template <int NV>
+AW_DEV void stage_pose(const DModel& m, Env& s, const DState& st, int env, int lane) {
+  if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
+  wsync();
+  stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
+  stage_kinematics(m, s, lane);
+}
+AW_DEV void view_cam(const Env& s, const float* rec, int body, float* lcam, int tid, float (&cam)[AW_CAM_FLOATS]) {
+  compose_view(s, rec, body, lcam, tid);
+  __syncthreads();
+  for (int k = 0; k < AW_CAM_FLOATS; k++)
+    cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
 }
 
 // depth frame of every env's current state: wave 0 runs the kinematics, then all four waves
@@ -364,12 +359,7 @@ __global__ void __launch_bounds__(256) k_depth(DModel m, DState st, int n, CamRe
   __shared__ RGeoms rg;
   const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (env >= n) return;
-  if (tid < 64) {
-    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
-    wsync();
-    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-    stage_kinematics(m, s, lane);
-  }
+  if (tid < 64) stage_pose<NV>(m, s, st, env, lane);
   __syncthreads();
   render_geoms(m, s, rg, cam.c, tid, 256);
   __syncthreads();
@@ -389,12 +379,7 @@ __global__ void __launch_bounds__(256) k_rgb(DModel m, DState st, int n, CamRec 
   __shared__ RColors rc;
   const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (env >= n) return;
-  if (tid < 64) {
-    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
-    wsync();
-    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-    stage_kinematics(m, s, lane);
-  }
+  if (tid < 64) stage_pose<NV>(m, s, st, env, lane);
   __syncthreads();
   render_geoms(m, s, rg, cam.c, tid, 256);
   render_sites(m, s, rg, cam.c, tid, 256);
@@ -408,12 +393,10 @@ __global__ void __launch_bounds__(256) k_rgb(DModel m, DState st, int n, CamRec 
 
 // several cameras per launch, each in the frame of a body, optionally one record per env and view
 // (aw_render_views): k_rgb's (RGB) or k_depth's structure with the staging and the kinematics done
-// once per env, then per view the world record composed into LDS (compose_view), the pixel boxes
-// and the headlight rebuilt against it and the spans cast.  The aw_render.h functions are the ones
-// k_depth / k_rgb call, so a world-frame view writes their frames bit for bit.  Every barrier of
-// the view loop is uniform: nviews is a kernel argument and the early return takes the whole block.
-// dwords: every frame's base and size are multiples of 4 bytes (launch_views).
-struct NoColors {};
+// once per env, then per view the camera (view_cam), the pixel boxes and the headlight rebuilt
+// against it and the spans cast.  The aw_render.h functions are the ones k_depth / k_rgb call, so a
+// world-frame view writes their frames bit for bit.  dwords: rgb_dwords.
+struct NoLds {};   // the LDS block an instantiation does not have
 template <int TASK, bool RGB>
 __global__ void __launch_bounds__(256) k_views(DModel m, DState st, int n, ViewsRec views, int nviews,
                                                const float* __restrict__ env_cam, LookRec look, int W, int H, int ss,
@@ -421,27 +404,18 @@ __global__ void __launch_bounds__(256) k_views(DModel m, DState st, int n, Views
   constexpr int NV = Tree<TASK>::NV;
   __shared__ Env s;
   __shared__ RGeoms rg;
-  __shared__ std::conditional_t<RGB, RColors, NoColors> rc;
+  __shared__ std::conditional_t<RGB, RColors, NoLds> rc;
   __shared__ float lcam[AW_CAM_FLOATS];
   const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (env >= n) return;
-  if (tid < 64) {
-    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
-    wsync();
-    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-    stage_kinematics(m, s, lane);
-  }
+  if (tid < 64) stage_pose<NV>(m, s, st, env, lane);
   __syncthreads();
   if constexpr (RGB) render_colors_env(m, s, rc, look.c, tid, 256);
   const size_t np = (size_t)W * H;
   for (int v = 0; v < nviews; v++) {
     const size_t frame = (size_t)env * nviews + v;
-    compose_view(s, env_cam ? env_cam + frame * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid);
-    __syncthreads();
-    // the record is uniform over the block: held in scalar registers, as k_rgb's kernel argument is
     float cam[AW_CAM_FLOATS];
-    for (int k = 0; k < AW_CAM_FLOATS; k++)
-      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    view_cam(s, env_cam ? env_cam + frame * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid, cam);
     render_geoms(m, s, rg, cam, tid, 256);
     if constexpr (RGB) {
       render_sites(m, s, rg, cam, tid, 256);
@@ -460,35 +434,35 @@ __global__ void __launch_bounds__(256) k_views(DModel m, DState st, int n, Views
   }
 }
 
-// k_views<TASK, true> with the handle's appearance state (aw_set_appearance), in instantiations of
-// its own so that k_views stays the kernel it was.  APP: env e's colour and light records come from
-// app.col + e ne COL_W / app.light + e nlight LIGHT_W and its look from app.look + e AW_LOOK_FLOATS,
-// each where the pointer is given (nullptr: the model's records / the launch's host look).  The look
-// row goes through LDS into scalar registers once per block, as the camera record does.  SHADOW:
-// shade casts the shadow rays (aw_render.h occluded) against the candidates of the lights' occluder
-// grids (RShadow: 10 KiB of LDS, built per view behind two more uniform barriers).  waves_per_eu(4):
-// left alone the shadow instantiations take 142 VGPRs, three waves per SIMD; capped at 128 (48 bytes
-// of scratch) they run four, which is what 39.7 KiB of LDS allows anyway -- 2.68 -> 2.20 ms per
-// 64x64 frame of 8 192 hammer envs.  The instantiations without shadows take 91 and are not affected.  Whatever the per-env records hold, every
-// output index is blockIdx.x, the view and the lane: a workgroup writes only its own env's frames.
+// k_views<TASK, true> with the handle's appearance state (aw_set_appearance).  A kernel of its own,
+// not a second wrapper over one body: with the view loop in a shared inlined body the depth and the
+// shadow frames measured 1-2 % slower than from these two copies.  What differs from
+// k_views: APP: env e's colour and light records come from app.col + e ne COL_W / app.light + e
+// nlight LIGHT_W and its look from app.look + e AW_LOOK_FLOATS, each where the pointer is given
+// (nullptr: the model's records / the launch's host look).  The look row goes through LDS into scalar
+// registers once per block, as the camera record does.  SHADOW: shade casts the shadow rays
+// (aw_render.h occluded) against the candidates of the lights' occluder grids (RShadow: 10 KiB of
+// LDS, built per view behind two more uniform barriers).  waves_per_eu(4): left alone the shadow
+// instantiations take 142 VGPRs, three waves per SIMD; capped at 128 (48 bytes of scratch) they run
+// four, which is what 39.7 KiB of LDS allows anyway -- 2.68 -> 2.20 ms per 64x64 frame of 8 192
+// hammer envs.  The instantiations without shadows take 91 and are not affected.  Whatever the per-env
+// records hold, every output index is blockIdx.x, the view and the lane: a workgroup writes only its
+// own env's frames.
 template <int TASK, bool APP, bool SHADOW>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_views_app(DModel m, DState st, int n, ViewsRec views, int nviews,
-                                                   const float* __restrict__ env_cam, LookRec look, AppRec app, int W,
-                                                   int H, int ss, unsigned char* out, int dwords, float* depth) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_views_app(DModel m, DState st, int n, ViewsRec views, int nviews, const float* __restrict__ env_cam, LookRec look,
+            AppRec app, int W, int H, int ss, unsigned char* out, int dwords, float* depth) {
   constexpr int NV = Tree<TASK>::NV;
   __shared__ Env s;
   __shared__ RGeoms rg;
   __shared__ RColors rc;
   __shared__ float lcam[AW_CAM_FLOATS];
   __shared__ float llook[AW_LOOK_FLOATS];
-  __shared__ std::conditional_t<SHADOW, RShadow, NoColors> sh;
+  __shared__ std::conditional_t<SHADOW, RShadow, NoLds> sh;
   const int env = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (env >= n) return;
   if (tid < 64) {
-    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
-    wsync();
-    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-    stage_kinematics(m, s, lane);
+    stage_pose<NV>(m, s, st, env, lane);
   } else if (tid < 64 + AW_LOOK_FLOATS) {
     const int k = tid - 64;
     llook[k] = APP && app.look ? app.look[(size_t)env * AW_LOOK_FLOATS + k] : look.c[k];
@@ -503,15 +477,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   const size_t np = (size_t)W * H;
   for (int v = 0; v < nviews; v++) {
     const size_t frame = (size_t)env * nviews + v;
-    compose_view(s, env_cam ? env_cam + frame * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid);
-    __syncthreads();
     float cam[AW_CAM_FLOATS];
-    for (int k = 0; k < AW_CAM_FLOATS; k++)
-      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    view_cam(s, env_cam ? env_cam + frame * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid, cam);
     render_geoms(m, s, rg, cam, tid, 256);
     render_sites(m, s, rg, cam, tid, 256);
     render_headlight(rc, cam, lk, tid);
-    if (SHADOW && !(APP && app.light)) render_castshadow(m, rc, lk, tid);   // (behind the barrier above: the records are staged)
+    if (SHADOW && !(APP && app.light)) render_castshadow(m, rc, lk, tid);   // (behind view_cam's barrier: staged)
     __syncthreads();
     const RShadow* shp = nullptr;
     if constexpr (SHADOW) {   // the lights' occluder grids over the poses render_geoms just wrote
@@ -529,9 +500,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   }
 }
 
-// segmentation frames (aw_render_labels): k_views<TASK, false>'s structure -- the staging and the
-// kinematics once per env, per view compose_view, the pixel boxes and the 64-pixel spans -- writing
-// one int32 label per pixel (aw_render.h render_span_labels) and optionally the depth frame.
+// segmentation frames (aw_render_labels): k_views<TASK, false>'s structure, writing one int32 label
+// per pixel (aw_render.h render_span_labels) and optionally the depth frame.
 // SITES: the visible sites join the entries.  The workgroup renders env env_ids[blockIdx.x] (NULL:
 // blockIdx.x) into output row blockIdx.x; an id outside [0, n) is uniform over the block, which
 // leaves before its first barrier with its row untouched.  The env id selects what is read (the
@@ -549,26 +519,16 @@ __global__ void __launch_bounds__(256) k_labels(DModel m, DState st, int n, View
   const int tid = threadIdx.x, lane = tid & 63;
   const int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
   if (env < 0 || env >= n) return;
-  if (tid < 64) {
-    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
-    wsync();
-    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-    stage_kinematics(m, s, lane);
-  } else if (tid < 64 + MAXRG) {
-    slut[tid - 64] = lut.v[tid - 64];
-  }
+  if (tid < 64) stage_pose<NV>(m, s, st, env, lane);
+  else if (tid < 64 + MAXRG) slut[tid - 64] = lut.v[tid - 64];
   __syncthreads();
   const int ns = SITES ? m.nrsite : 0;
   const size_t np = (size_t)W * H;
   for (int v = 0; v < nviews; v++) {
     const size_t frame = (size_t)blockIdx.x * nviews + v;
-    compose_view(s, env_cam ? env_cam + ((size_t)env * nviews + v) * AW_CAM_FLOATS : views.c[v], views.body[v], lcam,
-                 tid);
-    __syncthreads();
-    // the record is uniform over the block: held in scalar registers, as in k_views
     float cam[AW_CAM_FLOATS];
-    for (int k = 0; k < AW_CAM_FLOATS; k++)
-      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    view_cam(s, env_cam ? env_cam + ((size_t)env * nviews + v) * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid,
+             cam);
     render_geoms(m, s, rg, cam, tid, 256);
     if constexpr (SITES) render_sites(m, s, rg, cam, tid, 256);
     __syncthreads();
@@ -579,11 +539,10 @@ __global__ void __launch_bounds__(256) k_labels(DModel m, DState st, int n, View
   }
 }
 
-// point-cloud candidates (aw_render_cloud): k_labels' structure -- the staging and the kinematics
-// once per env, per view compose_view, the pixel boxes and the 64-pixel spans -- keeping, of every
-// pixel that passes render_span_cloud (a hit on a kept entry inside the crop box), the world point
-// and the flat pixel index v H W + p, compacted in ascending pixel order into the first cap slots
-// of output row blockIdx.x.  No atomics: the four waves cast one round of 256 consecutive pixels,
+// point-cloud candidates (aw_render_cloud): k_labels' structure, keeping, of every pixel that passes
+// render_span_cloud (a hit on a kept entry inside the crop box), the world point and the flat pixel
+// index v H W + p, compacted in ascending pixel order into the first cap slots of output row
+// blockIdx.x.  No atomics: the four waves cast one round of 256 consecutive pixels,
 // each ballots its candidates and leaves the popcount in LDS; behind one barrier a candidate's slot
 // is the running base (the candidates of all earlier rounds and views, carried identically by every
 // thread) + the counts of the lower waves + the candidates on lower lanes.  The counts are double
@@ -604,12 +563,7 @@ __global__ void __launch_bounds__(256) k_cloud(DModel m, DState st, int n, Views
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
   if (env < 0 || env >= n) return;
-  if (tid < 64) {
-    if (lane < NV) { s.qpos[lane] = st.qpos[(size_t)env * m.nq + lane]; s.qlo[lane] = 0.f; }
-    wsync();
-    stage_model(m, s, st.params + (size_t)env * m.nparam, lane);
-    stage_kinematics(m, s, lane);
-  }
+  if (tid < 64) stage_pose<NV>(m, s, st, env, lane);
   __syncthreads();
   const int ns = SITES ? m.nrsite : 0;
   const int np = W * H;
@@ -618,13 +572,9 @@ __global__ void __launch_bounds__(256) k_cloud(DModel m, DState st, int n, Views
   int* prow = pix ? pix + (size_t)blockIdx.x * c.cap : nullptr;
   int base = 0, round = 0;
   for (int v = 0; v < nviews; v++) {
-    compose_view(s, env_cam ? env_cam + ((size_t)env * nviews + v) * AW_CAM_FLOATS : views.c[v], views.body[v], lcam,
-                 tid);
-    __syncthreads();
-    // the record is uniform over the block: held in scalar registers, as in k_views
     float cam[AW_CAM_FLOATS];
-    for (int k = 0; k < AW_CAM_FLOATS; k++)
-      cam[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lcam[k])));
+    view_cam(s, env_cam ? env_cam + ((size_t)env * nviews + v) * AW_CAM_FLOATS : views.c[v], views.body[v], lcam, tid,
+             cam);
     render_geoms(m, s, rg, cam, tid, 256);
     if constexpr (SITES) render_sites(m, s, rg, cam, tid, 256);
     __syncthreads();
@@ -748,70 +698,58 @@ template <int TASK>
 static void launch_depth(aw_handle* h, const CamRec& cam, int W, int H, float* out, hipStream_t st) {
   hipLaunchKernelGGL((k_depth<TASK>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, cam, W, H, out);
 }
+// whole-dword stores of RGB frames: frame f starts at byte f * 3 W H of rgb, so the frame size and
+// the output base both have to be multiples of 4 bytes
+static int rgb_dwords(const uint8_t* rgb, int W, int H) {
+  return rgb && (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;
+}
 template <int TASK>
 static void launch_rgb(aw_handle* h, const CamRec& cam, const LookRec& look, int W, int H, int ss, uint8_t* rgb,
                        float* depth, hipStream_t st) {
-  // whole-dword stores need a frame size and a base that are multiples of 4 bytes
-  const int dwords = (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;
   hipLaunchKernelGGL((k_rgb<TASK>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, cam, look, W, H, ss, rgb,
-                     dwords, depth);
+                     rgb_dwords(rgb, W, H), depth);
 }
+// depth only: k_views<TASK, false>; RGB: k_views<TASK, true>, or while the handle holds per-env
+// tables and / or casts shadows (has_appearance) the k_views_app instantiation of that state
 template <int TASK>
 static void launch_views(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam, const LookRec& look,
                          int W, int H, int ss, uint8_t* rgb, float* depth, hipStream_t st) {
-  if (!rgb) {
-    hipLaunchKernelGGL((k_views<TASK, false>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
-                       env_cam, look, W, H, ss, nullptr, 0, depth);
-    return;
-  }
-  // frame f starts at byte f * 3 W H of rgb: whole-dword stores need every frame's base to be a
-  // multiple of 4 bytes, so the frame size and the output base both have to be
-  const int dwords = (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;
-  hipLaunchKernelGGL((k_views<TASK, true>), dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
-                     env_cam, look, W, H, ss, rgb, dwords, depth);
-}
-// aw_render_views' RGB launch while the handle holds per-env tables and / or casts shadows
-template <int TASK>
-static void launch_views_app(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam,
-                             const LookRec& look, int W, int H, int ss, uint8_t* rgb, float* depth, hipStream_t st) {
-  const int dwords = (3 * (size_t)W * H) % 4 == 0 && (uintptr_t)rgb % 4 == 0;   // as launch_views
-  const bool app = h->app.col || h->app.light || h->app.look;
-  auto go = [&](auto kernel) {
+  auto go = [&](auto kernel, auto... app) {
     hipLaunchKernelGGL(kernel, dim3(h->nenv), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews, env_cam, look,
-                       h->app, W, H, ss, rgb, dwords, depth);
+                       app..., W, H, ss, rgb, rgb_dwords(rgb, W, H), depth);
   };
-  if (app && h->shadows) go(k_views_app<TASK, true, true>);
-  else if (app) go(k_views_app<TASK, true, false>);
-  else go(k_views_app<TASK, false, true>);
+  if (!rgb) go(k_views<TASK, false>);
+  else if (!has_appearance(h)) go(k_views<TASK, true>);
+  else if (!h->shadows) go(k_views_app<TASK, true, false>, h->app);
+  else if (h->app.any()) go(k_views_app<TASK, true, true>, h->app);
+  else go(k_views_app<TASK, false, true>, h->app);
 }
 // grid: the output rows (the selected envs, or all of them)
 template <int TASK>
 static void launch_labels(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam, const int32_t* env_ids,
                           int grid, const LutRec& lut, int32_t background, int sites, int W, int H, int32_t* labels,
                           float* depth, hipStream_t st) {
-  if (sites)
-    hipLaunchKernelGGL((k_labels<TASK, true>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
-                       env_cam, env_ids, lut, background, W, H, labels, depth);
-  else
-    hipLaunchKernelGGL((k_labels<TASK, false>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
-                       env_cam, env_ids, lut, background, W, H, labels, depth);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews, env_cam, env_ids, lut,
+                       background, W, H, labels, depth);
+  };
+  sites ? go(k_labels<TASK, true>) : go(k_labels<TASK, false>);
 }
 template <int TASK>
 static void launch_cloud(aw_handle* h, const ViewsRec& views, int nviews, const float* env_cam, const int32_t* env_ids,
                          int grid, const CloudRec& c, int sites, int W, int H, float* xyz, int32_t* pix, int32_t* count,
                          hipStream_t st) {
-  if (sites)
-    hipLaunchKernelGGL((k_cloud<TASK, true>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
-                       env_cam, env_ids, c, W, H, xyz, pix, count);
-  else
-    hipLaunchKernelGGL((k_cloud<TASK, false>), dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews,
-                       env_cam, env_ids, c, W, H, xyz, pix, count);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, h->m, h->st, h->nenv, views, nviews, env_cam, env_ids, c, W,
+                       H, xyz, pix, count);
+  };
+  sites ? go(k_cloud<TASK, true>) : go(k_cloud<TASK, false>);
 }
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>, launch_set_ids<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
-                              launch_labels<TASK>, launch_cloud<TASK>, launch_views_app<TASK>};
+                              launch_labels<TASK>, launch_cloud<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();
