@@ -279,6 +279,55 @@ int aw_forward_dump(aw_handle* h, int env, const float* ctrl, float* out, void* 
 #define AW_DUMP_SIZE_WIDE 6120
 int aw_forward_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, void* stream);
 
+/* Dynamics queries (k_dyn): the model-based half of sim.data for a chosen subset of envs, on demand --
+ * point and body Jacobians (mujoco-py get_site_jacp / jacr, get_body_jacp / jacr), linear and angular
+ * velocities (get_body_xvelp / xvelr, get_site_xvelp / xvelr), the joint-space inertia and its inverse,
+ * and the three terms of qfrc_smooth.  One wave per output row composes the forward's own position
+ * and velocity stages (kinematics, mj_comPos, mj_comVel, mj_rne, mj_passive, mj_fwdActuation, mj_crb,
+ * the tree-sparse LDL') and stores what was asked for; no collision, no constraint solve.
+ *   VALUES are those of mj_forward's position and velocity stages AT THE GIVEN STATE -- what mujoco-py
+ * shows after sim.forward() -- not the pre-integration values of the last substep that the AW_DATA_*
+ * views hold after a step.
+ *   env_ids / n_sel: as in aw_render_labels.  NULL: every env, n = n_envs; else a DEVICE int32 array of
+ * n = n_sel ids and output row k is env env_ids[k]; an id outside [0, n_envs) leaves row k of every
+ * output untouched; ids may repeat.
+ *   points: a HOST array of npoints (0..AW_DYN_MAXPOINTS) records, handed to the kernel by value:
+ * kind AW_PT_BODY (the body frame's origin xpos[id]), AW_PT_BODYCOM (the body's centre of mass
+ * xipos[id]) or AW_PT_SITE (site_xpos[id]); the point moves with body id (the site's body).
+ *   qpos [n][nq], qvel [n][nv]: NULL (the env's own stored state) or DEVICE arrays indexed by OUTPUT
+ * ROW that replace the env's values for this evaluation only; nothing of the simulation is written.
+ * The model parameters are always the env's own (mass, position and size variations, reset draws).
+ *   ctrl [n][nu]: NULL (zero) or DEVICE raw controls indexed by output row, as aw_forward_dump takes
+ * them; only qfrc_actuator reads them.
+ *   out: DEVICE fp32 buffers, any may be NULL (then not computed; whole stages are skipped when no
+ * requested output needs them):
+ *     qM, qMinv [n][nv][nv]   dense symmetric: mj_fullM's matrix (armature on the diagonal) and its
+ *                             inverse from the tree factorisation (mj_factorM / mj_solveM)
+ *     qfrc_bias, qfrc_passive, qfrc_actuator [n][nv]   mj_rne with flg_acc = 0, -damping qvel, the
+ *                             actuator forces mapped to the dofs; passive - bias + actuator = qfrc_smooth
+ *     xvel [n][nbody][6]      (angular, linear at xpos[b]) in world axes: mj_objectVelocity, flg_local 0
+ *     point_pos [n][npoints][3], point_vel [n][npoints][6]   the points and their (angular, linear) velocity
+ *     jacp, jacr [n][npoints][3][nv]   mj_jac: column i is zero unless dof i moves the point's body b,
+ *                             else jacr = cdof_i[0:3], jacp = cdof_i[3:6] + cdof_i[0:3] x (p -
+ *                             subtree_com[body_rootid[b]]); body 0 has zero Jacobians
+ * The handle's aw_set_option disable flags (gravity, passive, actuation, clampctrl) act as in the forward.
+ * Enqueues on `stream`, allocates nothing, does not wait.
+ * AW_EINVAL (every other call still works afterwards): NULL h or out, every output NULL, npoints
+ * outside 0..AW_DYN_MAXPOINTS or NULL points with npoints > 0, a point output (point_pos, point_vel,
+ * jacp, jacr) with npoints == 0, an unknown kind, an id outside its range, n_sel < 1 with env_ids. */
+enum { AW_PT_BODY = 0, AW_PT_BODYCOM = 1, AW_PT_SITE = 2 };
+#define AW_DYN_MAXPOINTS 16
+typedef struct { int32_t kind, id; } aw_dyn_point;
+typedef struct {
+  float *qM, *qMinv;
+  float *qfrc_bias, *qfrc_passive, *qfrc_actuator;
+  float *xvel;
+  float *point_pos, *point_vel;
+  float *jacp, *jacr;
+} aw_dyn_out;
+int aw_dynamics(aw_handle* h, const int32_t* env_ids, int n_sel, const aw_dyn_point* points, int npoints,
+                const float* qpos, const float* qvel, const float* ctrl, const aw_dyn_out* out, void* stream);
+
 /* Depth camera observation (the reference renders RGB through OpenGL:
  * headless_observer.py:20-52 -- free camera azimuth 90, distance 4.5, elevation from the
  * object / last-camera direction, 640x480 frame centre-cropped to 128x128 and resized to

@@ -84,6 +84,31 @@ class AppearanceBufs(ctypes.Structure):
 
 
 AW_COL_FLOATS, AW_LIGHT_FLOATS, AW_LOOK_FLOATS = 8, 24, 7
+
+# dynamics queries (include/adroit_wave.h aw_dynamics): point kinds, the point capacity, the outputs in
+# aw_dyn_out's order with their row shapes as functions of (nv, nbody, npoints), and which need points
+AW_PT_BODY, AW_PT_BODYCOM, AW_PT_SITE = 0, 1, 2
+AW_DYN_MAXPOINTS = 16
+DYN_OUTPUTS = ("qM", "qMinv", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "xvel", "point_pos", "point_vel",
+               "jacp", "jacr")
+DYN_POINT_OUTPUTS = ("point_pos", "point_vel", "jacp", "jacr")
+
+
+def dyn_shape(name: str, nv: int, nbody: int, npoints: int) -> tuple:
+    """row shape of one aw_dynamics output"""
+    return dict(qM=(nv, nv), qMinv=(nv, nv), qfrc_bias=(nv,), qfrc_passive=(nv,), qfrc_actuator=(nv,),
+                xvel=(nbody, 6), point_pos=(npoints, 3), point_vel=(npoints, 6), jacp=(npoints, 3, nv),
+                jacr=(npoints, 3, nv))[name]
+
+
+class DynPoint(ctypes.Structure):
+    """aw_dyn_point: a point of aw_dynamics (kind AW_PT_*, body or site id)"""
+    _fields_ = [("kind", ctypes.c_int32), ("id", ctypes.c_int32)]
+
+
+class DynOut(ctypes.Structure):
+    """aw_dyn_out: the device fp32 output buffers of aw_dynamics, NULL where not requested"""
+    _fields_ = [(k, _vp) for k in DYN_OUTPUTS]
 # slots of a record vector [col | light | look] that aw_appearance_sample copies from ``lo``
 LIGHT_FLAG_SLOTS = (18, 20, 21)
 LOOK_FLAG_SLOT = 6
@@ -200,6 +225,10 @@ def load():
         L.aw_clone_envs.argtypes = [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]
         for f in ("aw_set_state_ids", "aw_get_state_ids", "aw_clone_envs"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "aw_dynamics"):
+        L.aw_dynamics.argtypes = [_vp, _vp, ctypes.c_int, ctypes.POINTER(DynPoint), ctypes.c_int, _vp, _vp, _vp,
+                                  ctypes.POINTER(DynOut), _vp]
+        L.aw_dynamics.restype = ctypes.c_int
     if hasattr(L, "aw_policy_mlp"):
         L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, _vp]
@@ -219,7 +248,8 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_get_state_ids", "aw_clone_envs", "aw_status",
            "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
            "aw_set_episode",
-           "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_stage_profile", "aw_render_depth", "aw_render_rgb",
+           "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_dynamics", "aw_stage_profile", "aw_render_depth",
+           "aw_render_rgb",
            "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_render_cloud", "aw_cloud_fps",
            "aw_policy_mlp", "aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample",
            "aw_collide_test", "aw_last_error")
@@ -783,6 +813,42 @@ class Sim:
         o = (out64 if fp64 else out).cpu().numpy().astype(np.float64)
         c = cnt.cpu().numpy()
         return [o[i, :c[i]] for i in range(n)]
+
+    def dynamics(self, out: dict, points=(), env_ids=None, qpos=None, qvel=None, ctrl=None,
+                 n_sel: Optional[int] = None, npoints: Optional[int] = None):
+        """Dynamics queries of the selected envs in one launch (include/adroit_wave.h aw_dynamics).
+        out: name -> device fp32 tensor for the outputs wanted (DYN_OUTPUTS; [n, ...] with the row
+        shapes of ``dyn_shape``), written in place.  points: host (kind, id) pairs (AW_PT_*).  env_ids
+        [n] (device, int32): output row k is env env_ids[k] (None: every env, n = n_envs).  qpos
+        [n, nq], qvel [n, nv] (device, fp32): replace the env's own state for this evaluation only;
+        ctrl [n, nu]: raw controls for qfrc_actuator (None: zero).  n_sel, npoints: the counts handed
+        to the library in place of the arguments' own lengths."""
+        import torch
+        pts = list(points)
+        arr = (DynPoint * max(len(pts), 1))()
+        for k, (kind, idx) in enumerate(pts):
+            arr[k].kind, arr[k].id = int(kind), int(idx)
+        n = self.n_envs
+        if env_ids is not None:
+            _ids_ok(env_ids, "dynamics: env_ids")
+            n = int(env_ids.shape[0])
+        npt = len(pts)
+        unknown = set(out) - set(DYN_OUTPUTS)
+        assert not unknown, f"dynamics: unknown outputs {sorted(unknown)}"
+        c = DynOut()
+        for k, t in out.items():
+            if t is None:
+                continue
+            shape = (n,) + dyn_shape(k, self.nv, self.nbody, npt)
+            assert tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda, \
+                f"dynamics: {k} must be a device fp32 {list(shape)}"
+            setattr(c, k, t.data_ptr())
+        for t, w, k in ((qpos, self.nq, "qpos"), (qvel, self.nv, "qvel"), (ctrl, self.nu, "ctrl")):
+            assert t is None or (tuple(t.shape) == (n, w) and t.dtype == torch.float32 and t.is_contiguous()
+                                 and t.is_cuda), f"dynamics: {k} must be a device fp32 [{n}, {w}]"
+        _check(load().aw_dynamics(self.h, _ptr(env_ids), n if n_sel is None else int(n_sel), arr,
+                                  npt if npoints is None else int(npoints), _ptr(qpos), _ptr(qvel), _ptr(ctrl),
+                                  ctypes.byref(c), _stream()))
 
     def forward_dump(self, env: int, ctrl=None, wide: bool = False) -> dict:
         """one forward of env `env` (ctrl: raw controls or None = 0) and its internals; wide=True runs it

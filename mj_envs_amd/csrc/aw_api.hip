@@ -788,6 +788,32 @@ int aw_forward_dump_wide(aw_handle* h, int env, const float* ctrl, float* out, v
   return AW_OK;
 }
 
+int aw_dynamics(aw_handle* h, const int32_t* env_ids, int n_sel, const aw_dyn_point* points, int npoints,
+                const float* qpos, const float* qvel, const float* ctrl, const aw_dyn_out* out, void* stream) {
+  if (!h || !out) return fail(AW_EINVAL, "aw_dynamics: null handle or out");
+  const bool pt_out = out->point_pos || out->point_vel || out->jacp || out->jacr;
+  if (!pt_out && !out->qM && !out->qMinv && !out->qfrc_bias && !out->qfrc_passive && !out->qfrc_actuator && !out->xvel)
+    return fail(AW_EINVAL, "aw_dynamics: no output requested");
+  if (npoints < 0 || npoints > AW_DYN_MAXPOINTS || (npoints > 0 && !points))
+    return fail(AW_EINVAL, "aw_dynamics: npoints must be 0..AW_DYN_MAXPOINTS, with points given");
+  if (pt_out && npoints == 0) return fail(AW_EINVAL, "aw_dynamics: a point output needs npoints >= 1");
+  if (env_ids && n_sel < 1) return fail(AW_EINVAL, "aw_dynamics: n_sel must be >= 1 with env_ids");
+  DynPts pts = {};   // a kernel argument, as the views of the render calls are
+  for (int p = 0; p < npoints; p++) {
+    const int kind = points[p].kind, id = points[p].id;
+    if (kind != AW_PT_BODY && kind != AW_PT_BODYCOM && kind != AW_PT_SITE)
+      return fail(AW_EINVAL, "aw_dynamics: a point's kind is none of AW_PT_BODY, AW_PT_BODYCOM, AW_PT_SITE");
+    if (id < 0 || id >= (kind == AW_PT_SITE ? h->m.nsite : h->m.nbody))
+      return fail(AW_EINVAL, "aw_dynamics: a point's id is not a body / site of the model");
+    pts.kind[p] = kind;
+    pts.id[p] = id;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  h->ops->dyn(h, env_ids, env_ids ? n_sel : h->nenv, pts, npoints, qpos, qvel, ctrl, *out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
 int aw_render_depth(aw_handle* h, const float* cam, int width, int height, float* out, void* stream) {
   if (!h || !cam || !out || width <= 0 || height <= 0 || width > 4096 || height > 4096)
     return fail(AW_EINVAL, "aw_render_depth: bad arguments");

@@ -49,6 +49,10 @@ struct CloudRec {
   float box[6];
   int crop, frame_body, cap;
 };
+// the point table of one aw_dynamics launch (k_dyn, aw_dyn.h): kind (AW_PT_*) and object id per point
+struct DynPts {
+  int kind[AW_DYN_MAXPOINTS], id[AW_DYN_MAXPOINTS];
+};
 // the per-env appearance tables of aw_set_appearance (k_views_app): the caller's device buffers,
 // [N][ne][COL_W], [N][nlight][LIGHT_W], [N][AW_LOOK_FLOATS]; nullptr: the model's / the launch's look
 struct AppRec {
@@ -156,6 +160,8 @@ struct TaskOps {
                  int, int32_t*, float*, hipStream_t);
   void (*cloud)(aw_handle*, const ViewsRec&, int, const float*, const int32_t*, int, const CloudRec&, int, int, int,
                 float*, int32_t*, int32_t*, hipStream_t);
+  void (*dyn)(aw_handle*, const int32_t*, int, const DynPts&, int, const float*, const float*, const float*,
+              const aw_dyn_out&, hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 

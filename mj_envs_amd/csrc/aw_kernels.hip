@@ -1,7 +1,7 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
 // -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_set_state_ids, k_dump, k_depth, k_rgb, k_views,
-// k_views_app, k_labels, k_cloud, k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide
+// k_views_app, k_labels, k_cloud, k_dyn (aw_dyn.h), k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide
 // tier: k_step_wide, k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
 // env-step both tiers run is aw_step.h.  Written once: finish_forward (the tail of k_reset and the set-state kernels),
 // set_state_body (both set-state kernels), stage_pose / view_cam (the render kernels' prologue and per-view camera).
@@ -17,6 +17,9 @@
 #include "aw_handle.h"
 #include "aw_render.h"
 #include "aw_step.h"
+#ifndef AW_WIDE
+#include "aw_dyn.h"   // k_dyn: the fast-tier unit only
+#endif
 
 using namespace aw;
 
@@ -745,11 +748,18 @@ static void launch_cloud(aw_handle* h, const ViewsRec& views, int nviews, const 
   };
   sites ? go(k_cloud<TASK, true>) : go(k_cloud<TASK, false>);
 }
+// grid: the output rows (the selected envs, or all of them)
+template <int TASK>
+static void launch_dyn(aw_handle* h, const int32_t* env_ids, int grid, const DynPts& pts, int npoints, const float* qpos,
+                       const float* qvel, const float* ctrl, const aw_dyn_out& out, hipStream_t st) {
+  hipLaunchKernelGGL((k_dyn<TASK>), dim3(grid), dim3(64), 0, st, h->m, h->st, h->nenv, env_ids, pts, npoints, qpos, qvel,
+                     ctrl, out);
+}
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>, launch_set_ids<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
-                              launch_labels<TASK>, launch_cloud<TASK>};
+                              launch_labels<TASK>, launch_cloud<TASK>, launch_dyn<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();

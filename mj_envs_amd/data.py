@@ -158,12 +158,17 @@ class DataViews:
 
 class EnvData:
     """``env.data`` of a single-env facade: float64 numpy copies of env 0, the contact arrays cut to
-    ncon (at most max_contacts)."""
+    ncon (at most max_contacts).  ``views`` None: the env was created with data=False and holds
+    none of them.  ``dynamics`` (``mj_envs_amd.dynamics.EnvDynamics``): mujoco-py's model-based
+    queries -- get_site_jacp, get_body_xvelp, qfrc_bias, qM_full ... -- evaluated on demand."""
 
     class _Contacts:
         pass
 
-    def __init__(self, views: DataViews):
+    def __init__(self, views: DataViews, dynamics=None):
+        self._dynamics = dynamics
+        if views is None:
+            return
         v = views
         for k in _KIN + ("qacc", "qfrc_constraint"):
             if k in v.__dict__:
@@ -180,3 +185,11 @@ class EnvData:
                 setattr(self.contact, k, a.astype(np.int32 if is_int else np.float64))
             frames = make_frame_np(self.contact.normal) if n else np.zeros((0, 3, 3))
             self.contact.force_world = np.einsum("ck,ckj->cj", self.contact.force, frames) if n else np.zeros((0, 3))
+
+    def __getattr__(self, name):     # only reached for names not set above
+        dyn = self.__dict__.get("_dynamics")
+        if dyn is not None and not name.startswith("_") and hasattr(type(dyn), name):
+            return getattr(dyn, name)
+        if name in GROUP_OF:
+            raise AttributeError(f"data.{name}: the {GROUP_OF[name]!r} group is not enabled (data=...)")
+        raise AttributeError(name)

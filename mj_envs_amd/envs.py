@@ -456,6 +456,23 @@ class AdroitVecEnv:
         self._read_sensors()
         return self.obs
 
+    # --- dynamics queries (mj_envs_amd/dynamics.py) --------------------------------------------
+    def dynamics(self, points=None, env_ids=None, want=("point_pos", "point_vel", "jacp", "jacr"), qpos=None,
+                 qvel=None, actions=None, ctrl=None, out=None):
+        """Jacobians, velocities, the joint-space inertia and the force terms of every env, or of
+        ``env_ids`` (a list, a numpy array or a device int32 tensor; ids may repeat), in one launch
+        (``aw_dynamics``).  ``points``: a ``dynamics.points(...)`` table (None: no points).  ``want``:
+        names out of qM, qMinv, qfrc_bias, qfrc_passive, qfrc_actuator, xvel, point_pos, point_vel,
+        jacp, jacr; what is not wanted is not computed.  ``qpos`` [n, nq] / ``qvel`` [n, nv] (device,
+        one row per output row): a trial state used for this evaluation only -- the simulation is not
+        touched; None: the env's own.  ``actions`` [n, nu] (normalised, mapped through act_mid /
+        act_rng as the step maps them) or ``ctrl`` [n, nu] (raw), not both: the controls
+        ``qfrc_actuator`` is evaluated with (None: zero).  ``out``: an earlier result whose buffers
+        are reused where the shapes agree.  Returns a ``dynamics.Dynamics``.  The values are those
+        of mj_forward at that state (mujoco-py after ``sim.forward()``), not the ``data`` views'."""
+        from .dynamics import evaluate
+        return evaluate(self, points, env_ids, want, qpos, qvel, actions, ctrl, out)
+
     def get_episode(self):
         """the running episode of every env: ep_len, ep_ret, ep_goal, and the finished-episode count"""
         import torch
@@ -554,6 +571,7 @@ class _AdroitEnv(_reference_base()):
         a = np.asarray(a, np.float32).reshape(1, -1)
         self._act.copy_(torch.from_numpy(a))
         obs, rew, term, _trunc, info = self.vec.step(self._act)
+        self._stepped = True            # data.qfrc_actuator: at these controls until the next reset
         self._obs = obs[0].cpu().numpy().copy()
         return self._obs, float(rew[0]), bool(term[0]), {"goal_achieved": bool(info["goal_achieved"][0])}
 
@@ -562,6 +580,7 @@ class _AdroitEnv(_reference_base()):
             self.seed(seed)
         s = int(self.np_random.integers(1, 2 ** 63 - 1))
         self.vec.reset(seed=s)
+        self._stepped = False
         self._obs = self.vec.obs[0].cpu().numpy().copy()
         return self._obs, {}
 
@@ -581,9 +600,24 @@ class _AdroitEnv(_reference_base()):
     def data(self):
         """``self.data`` of the reference (``sim.data``) after the last step / reset / set_env_state:
         float64 numpy copies of body_xpos, body_xquat, site_xpos, qacc, qfrc_constraint, ncon, nefc,
-        solver_iter, noslip_iter and contact.* cut to ncon (needs ``data=True`` or group names)"""
+        solver_iter, noslip_iter and contact.* cut to ncon (needs ``data=True`` or group names).
+        Whatever ``data`` was, the object also answers mujoco-py's model-based queries at the current
+        state (``dynamics.EnvDynamics``): ``get_site_jacp(name)``, ``get_site_jacr``, ``get_body_jacp``,
+        ``get_body_jacr``, ``get_site_xvelp``, ``get_site_xvelr``, ``get_body_xvelp``, ``get_body_xvelr``,
+        ``qfrc_bias``, ``qfrc_passive``, ``qfrc_actuator`` (at the last step's controls) and ``qM_full``."""
         from .data import EnvData
-        return EnvData(self.vec.data)
+        return EnvData(self.vec._data, dynamics=self._dynamics())
+
+    def _dynamics(self):
+        """the single env's dynamics queries, with the last step's raw controls"""
+        import torch
+        from .dynamics import EnvDynamics
+        a = self._act.clamp(-1.0, 1.0) if getattr(self, "_stepped", False) else None
+        ctrl = None
+        if a is not None:
+            ctrl = torch.as_tensor(self.vec.act_mid, device=self._dev) + a * torch.as_tensor(self.vec.act_rng,
+                                                                                               device=self._dev)
+        return EnvDynamics(self.vec, ctrl)
 
     def _params(self) -> np.ndarray:
         return self.vec.get_state()["params"][0].cpu().numpy().astype(np.float64)

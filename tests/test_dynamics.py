@@ -1,0 +1,196 @@
+"""Dynamics queries, CPU side: the fp64 checker (tests/dyn_checker.py) pinned against finite
+differences of the oracle and against the oracle's own identities, the point tables and argument
+checks of mj_envs_amd/dynamics.py, and the ctypes structures against include/adroit_wave.h."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import dyn_checker as dc
+from conftest import ENVS, REPO, load_task_model, make_oracle
+from mj_envs_amd import _native, dynamics
+from mj_envs_amd.tasks import sample_params
+
+
+def random_state(env_id, seed=3):
+    """(m, o, params, qpos, qvel, ctrl): a random configuration with nonzero velocities and controls"""
+    m, o = make_oracle(env_id)
+    rng = np.random.default_rng(seed)
+    P = sample_params(env_id, m, rng, 1)[0]
+    q = rng.uniform(-0.3, 0.3, o.nq)
+    v = rng.uniform(-1.0, 1.0, o.nv)
+    ctrl = m.task_act_mid + rng.uniform(-1, 1, o.nu) * m.task_act_rng
+    return m, o, P, q, v, ctrl
+
+
+@pytest.mark.parametrize("env_id", ENVS)
+def test_jacp_is_the_derivative_of_the_site_positions(env_id):
+    """nq == nv (slides and hinges only), so jacp = d site_xpos / d qpos: central differences
+    (h = 1e-6) of the oracle's site_xpos, every site, to 1e-8 (measured worst case 1.4e-10 against
+    |J| <= 1); and point_vel's linear part is jacp @ qvel to 1e-12 (measured 2e-16)."""
+    m, o, P, q, v, ctrl = random_state(env_id)
+    assert o.nq == o.nv
+    ns = o.nsite
+    pts = [(dc.PT_SITE, i) for i in range(ns)]
+    jacp = np.zeros((ns, 3, o.nv))
+    pvel = np.zeros((ns, 6))
+    for k0 in range(0, ns, 16):               # any number of points: the checker has no capacity
+        r = dc.evaluate(o, m, P, q, v, ctrl, pts[k0:k0 + 16])
+        jacp[k0:k0 + 16], pvel[k0:k0 + 16] = r["jacp"], r["point_vel"]
+    h = 1e-6
+    fd = np.zeros_like(jacp)
+    for i in range(o.nv):
+        d = np.zeros(o.nq)
+        d[i] = h
+        o.forward1(P, q + d, v, np.zeros(o.nv), ctrl)
+        hi = o.get("site_xpos").reshape(-1, 3).copy()
+        o.forward1(P, q - d, v, np.zeros(o.nv), ctrl)
+        lo = o.get("site_xpos").reshape(-1, 3).copy()
+        fd[:, :, i] = (hi - lo) / (2 * h)
+    err = np.abs(jacp - fd).max()
+    verr = np.abs(pvel[:, 3:] - jacp @ v).max()
+    print(f"{env_id}: max |jacp - fd| = {err:.2e}, max |v - J qvel| = {verr:.2e}")
+    assert np.abs(jacp).max() > 0.1
+    assert err < 1e-8
+    assert verr < 1e-12
+
+
+@pytest.mark.parametrize("env_id", ENVS)
+def test_force_identity_and_inverse(env_id):
+    """qfrc_passive - qfrc_bias + qfrc_actuator == qfrc_smooth in the oracle; the checker's qMinv is
+    inv(qM) of a symmetric positive definite qM; body 0 has zero Jacobians and velocity"""
+    m, o, P, q, v, ctrl = random_state(env_id, seed=4)
+    o.forward1(P, q, v, np.zeros(o.nv), ctrl)
+    base = dc.read_base(o)
+    np.testing.assert_allclose(base["qfrc_passive"] - base["qfrc_bias"] + base["qfrc_actuator"], base["qfrc_smooth"],
+                               rtol=0, atol=1e-12 * max(1.0, np.abs(base["qfrc_smooth"]).max()))
+    assert np.abs(base["qfrc_actuator"]).max() > 0 and np.abs(base["qfrc_bias"]).max() > 0
+    r = dc.derive(m, base, [(dc.PT_BODY, 0), (dc.PT_BODYCOM, m.name2id("body", "ffdistal"))])
+    M = r["qM"]
+    np.testing.assert_array_equal(M, M.T)
+    assert np.linalg.eigvalsh(M).min() > 0
+    np.testing.assert_array_equal(r["qMinv"], np.linalg.inv(M))
+    np.testing.assert_allclose(r["qMinv"] @ M, np.eye(o.nv), atol=1e-9)
+    assert not r["jacp"][0].any() and not r["jacr"][0].any() and not r["point_vel"][0].any()
+    assert r["jacp"][1].any()
+
+
+def test_points_resolve_names_and_report_errors():
+    m = load_task_model("relocate-v0")
+    t = dynamics.points(m, sites=["S_grasp"], bodies=["ffdistal", 0], body_coms=["Object"])
+    sid, bid, oid = m.name2id("site", "S_grasp"), m.name2id("body", "ffdistal"), m.name2id("body", "Object")
+    assert t.records == [(_native.AW_PT_SITE, sid), (_native.AW_PT_BODY, bid), (_native.AW_PT_BODY, 0),
+                         (_native.AW_PT_BODYCOM, oid)]
+    assert t.names == ["S_grasp", "ffdistal", "world", "Object:com"]
+    assert t.index("Object:com") == 3 and t.index(2) == 2 and len(t) == 4
+    with pytest.raises(KeyError, match="no point named"):
+        t.index("Object")
+    with pytest.raises(KeyError):
+        t.index(4)
+    with pytest.raises(KeyError, match="no site named 'nope'"):
+        dynamics.points(m, sites=["nope"])
+    with pytest.raises(KeyError, match="outside"):
+        dynamics.points(m, bodies=[m.nbody])
+    with pytest.raises(TypeError):
+        dynamics.points(m, bodies=[1.5])
+    with pytest.raises(ValueError, match="more than once"):
+        dynamics.points(m, bodies=["palm", "palm"])
+    with pytest.raises(ValueError, match="at most 16"):
+        dynamics.points(m, bodies=list(range(17)))
+    assert len(dynamics.points(m, bodies=list(range(16)))) == 16
+
+
+def test_check_dynamics_args():
+    chk = dynamics.check_dynamics_args
+    n, nq, nv, nu = 6, 30, 30, 24
+    assert chk(("jacp", "qM"), 2, n, nq, nv, nu) == ("qM", "jacp")        # aw_dyn_out's order
+    assert chk("qM", 0, n, nq, nv, nu) == ("qM",)
+    assert chk(("qfrc_actuator",), 0, n, nq, nv, nu, (n, nq), (n, nv), (n, nu), None) == ("qfrc_actuator",)
+    for want, npt, kw, msg in (
+            ((), 0, {}, "no output"),
+            (("jacq",), 1, {}, "unknown output"),
+            (("jacp",), 0, {}, "need points"),
+            (("qM",), 17, {}, "at most 16"),
+            (("qM",), 0, dict(qpos_shape=(n, nq + 1)), "qpos must be"),
+            (("qM",), 0, dict(qvel_shape=(n - 1, nv)), "qvel must be"),
+            (("qM",), 0, dict(ctrl_shape=(n, nu, 1)), "ctrl must be"),
+            (("qM",), 0, dict(actions_shape=(nu,)), "actions must be"),
+            (("qfrc_actuator",), 0, dict(actions_shape=(n, nu), ctrl_shape=(n, nu)), "give one")):
+        with pytest.raises(ValueError, match=msg):
+            chk(want, npt, n, nq, nv, nu, **kw)
+
+
+def test_dynamics_result_lookups():
+    m = load_task_model("pen-v0")
+    t = dynamics.points(m, sites=["S_grasp"], bodies=["Object"])
+    jp = np.arange(2 * 2 * 3 * 4).reshape(2, 2, 3, 4)
+    d = dynamics.Dynamics(t, dict(jacp=jp, point_pos=jp[..., 0]), m)
+    np.testing.assert_array_equal(d.jacp("Object"), jp[:, 1])
+    np.testing.assert_array_equal(d.pos("S_grasp"), jp[:, 0, :, 0])
+    assert d.jacp_all is jp
+    with pytest.raises(AttributeError, match="jacr was not wanted"):
+        d.jacr("Object")
+    with pytest.raises(AttributeError, match="qM was not wanted"):
+        d.qM
+    with pytest.raises(KeyError):
+        d.jacp("palm")
+
+
+def test_opspace_inertia():
+    import torch
+    g = torch.Generator().manual_seed(0)
+    A = torch.randn(3, 8, 8, generator=g, dtype=torch.float64)
+    M = A @ A.transpose(-1, -2) + 8 * torch.eye(8, dtype=torch.float64)
+    J = torch.randn(3, 3, 8, generator=g, dtype=torch.float64)
+    lam = dynamics.opspace_inertia(J, torch.linalg.inv(M))
+    ref = np.stack([np.linalg.inv(J[k].numpy() @ np.linalg.inv(M[k].numpy()) @ J[k].numpy().T) for k in range(3)])
+    np.testing.assert_allclose(lam.numpy(), ref, rtol=1e-10)
+
+
+def header_text():
+    return open(os.path.join(REPO, "include", "adroit_wave.h")).read()
+
+
+def test_ctypes_structures_match_the_header():
+    """field order, field types and sizes of aw_dyn_point / aw_dyn_out, the constants and the entry
+    point's parameter list, parsed from the header text"""
+    src = header_text()
+    pt = re.search(r"typedef struct \{([^}]*)\} aw_dyn_point;", src).group(1)
+    assert re.sub(r"\s+", " ", pt).strip() == "int32_t kind, id;"
+    assert [f[0] for f in _native.DynPoint._fields_] == ["kind", "id"]
+    assert all(f[1] is ctypes.c_int32 for f in _native.DynPoint._fields_)
+    assert ctypes.sizeof(_native.DynPoint) == 8
+    body = re.search(r"typedef struct \{([^}]*)\} aw_dyn_out;", src).group(1)
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            assert decl.startswith("float "), decl
+            fields += [x.strip().lstrip("*") for x in decl[len("float "):].split(",")]
+            assert all(x.strip().startswith("*") for x in decl[len("float "):].split(",")), decl
+    assert tuple(fields) == _native.DYN_OUTPUTS == tuple(f[0] for f in _native.DynOut._fields_)
+    assert tuple(fields) == dc.OUTPUTS
+    assert ctypes.sizeof(_native.DynOut) == len(fields) * ctypes.sizeof(ctypes.c_void_p)
+    kinds = re.search(r"enum \{ AW_PT_BODY = (\d+), AW_PT_BODYCOM = (\d+), AW_PT_SITE = (\d+) \};", src).groups()
+    assert tuple(int(k) for k in kinds) == (_native.AW_PT_BODY, _native.AW_PT_BODYCOM, _native.AW_PT_SITE)
+    assert (dc.PT_BODY, dc.PT_BODYCOM, dc.PT_SITE) == tuple(int(k) for k in kinds)
+    assert int(re.search(r"#define AW_DYN_MAXPOINTS (\d+)", src).group(1)) == _native.AW_DYN_MAXPOINTS
+    proto = re.search(r"int aw_dynamics\(([^)]*)\);", src).group(1)
+    params = [re.sub(r"\s+", " ", p).strip() for p in proto.split(",")]
+    assert params == ["aw_handle* h", "const int32_t* env_ids", "int n_sel", "const aw_dyn_point* points", "int npoints",
+                      "const float* qpos", "const float* qvel", "const float* ctrl", "const aw_dyn_out* out",
+                      "void* stream"]
+    L = _native.load()
+    assert len(L.aw_dynamics.argtypes) == len(params) and L.aw_dynamics.restype is ctypes.c_int
+    assert L.aw_dynamics.argtypes[3] is ctypes.POINTER(_native.DynPoint)
+    assert L.aw_dynamics.argtypes[8] is ctypes.POINTER(_native.DynOut)
+    assert [L.aw_dynamics.argtypes[i] for i in (2, 4)] == [ctypes.c_int, ctypes.c_int]
+
+
+def test_dyn_shapes():
+    shapes = {k: _native.dyn_shape(k, 30, 31, 5) for k in _native.DYN_OUTPUTS}
+    assert shapes == dict(qM=(30, 30), qMinv=(30, 30), qfrc_bias=(30,), qfrc_passive=(30,), qfrc_actuator=(30,),
+                          xvel=(31, 6), point_pos=(5, 3), point_vel=(5, 6), jacp=(5, 3, 30), jacr=(5, 3, 30))
+    assert set(_native.DYN_POINT_OUTPUTS) == {k for k in _native.DYN_OUTPUTS if _native.dyn_shape(k, 1, 1, 0)[0] == 0}
