@@ -547,6 +547,16 @@ int aw_collide_test(aw_handle* h, int n, const int32_t* types, const float* pos,
                     const float* size, const float* margin, float* out, int32_t* count, double* out64,
                     void* stream);
 
+/* Test hook: the conservative midphase cull (the narrowphase's *_may_touch) of n cases (device
+ * arrays): pair [n] (index into the model's pair list: explicit pairs, then candidates), and for the
+ * pair's two geoms in the pair's own order pos [n][2][3], quat [n][2][4] (w x y z) and size
+ * [n][2][3] -> info [n][6] = (keep, g1, g2, collider class, type of g1, type of g2) and margin [n]
+ * (the pair's margin, which the cull reads from the model).  Classes 0 (plane pairs) and 1 (sphere /
+ * capsule pairs) have no cull: keep = 1.  A pair index out of range: keep = -1, the rest unwritten.
+ * Used by the cull soundness test: keep = 0 only where the collider emits nothing. */
+int aw_midphase_test(aw_handle* h, int n, const int32_t* pair, const float* pos, const float* quat,
+                     const float* size, int32_t* info, float* margin, void* stream);
+
 /* Diagnostic: per-stage shader-clock cycles of k_step summed over all waves since the last
  * reset (40 counters, see aw_common.h PR_*).  Only libraries built with -DAW_STAGE_PROF
  * collect them; the product build returns AW_EUNSUPPORTED. */

@@ -184,6 +184,9 @@ def load():
     L.aw_stage_profile.argtypes = [_vp, ctypes.c_int]
     L.aw_collide_test.argtypes = [_vp, ctypes.c_int] + [_vp] * 9
     L.aw_collide_test.restype = ctypes.c_int
+    if hasattr(L, "aw_midphase_test"):
+        L.aw_midphase_test.argtypes = [_vp, ctypes.c_int] + [_vp] * 7
+        L.aw_midphase_test.restype = ctypes.c_int
     # (diagnostic builds of older revisions, selected with AW_LIB, may lack the newer entry points;
     # calling one of those then raises AttributeError)
     if hasattr(L, "aw_set_episode_totals"):
@@ -252,7 +255,7 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_render_rgb",
            "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_render_cloud", "aw_cloud_fps",
            "aw_policy_mlp", "aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample",
-           "aw_collide_test", "aw_last_error")
+           "aw_collide_test", "aw_midphase_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
           "noslip", "jt_touch", "euler", "task_obs", "reset", "checks")
@@ -813,6 +816,23 @@ class Sim:
         o = (out64 if fp64 else out).cpu().numpy().astype(np.float64)
         c = cnt.cpu().numpy()
         return [o[i, :c[i]] for i in range(n)]
+
+    def midphase_test(self, pair, pos, quat, size):
+        """midphase cull of n cases (test hook): pair [n] model pair ids, pos [n, 2, 3], quat [n, 2, 4],
+        size [n, 2, 3] of the pair's geoms in its own order -> dict of numpy arrays keep, g1, g2, cls,
+        type1, type2 (int32 [n]) and margin (fp32 [n], the pair's)"""
+        import torch
+        n = len(pair)
+        dev = self.torch_device
+        t = lambda a, dt=torch.float32: torch.tensor(np.asarray(a), dtype=dt, device=dev).contiguous()
+        args = [t(pair, torch.int32), t(pos), t(quat), t(size)]   # alive until the kernel ran
+        assert args[1].numel() == 6 * n and args[2].numel() == 8 * n and args[3].numel() == 6 * n
+        info = torch.zeros(n, 6, dtype=torch.int32, device=dev)
+        mg = torch.zeros(n, device=dev)
+        _check(load().aw_midphase_test(self.h, n, *[_ptr(a) for a in args], _ptr(info), _ptr(mg), _stream()))
+        i = info.cpu().numpy()
+        return dict(keep=i[:, 0], g1=i[:, 1], g2=i[:, 2], cls=i[:, 3], type1=i[:, 4], type2=i[:, 5],
+                    margin=mg.cpu().numpy())
 
     def dynamics(self, out: dict, points=(), env_ids=None, qpos=None, qvel=None, ctrl=None,
                  n_sel: Optional[int] = None, npoints: Optional[int] = None):

@@ -118,6 +118,35 @@ __global__ void __launch_bounds__(64) k_collide_test(DModel m, int n, const int*
   }
 }
 
+// Test hook (aw_midphase_test): the conservative midphase cull of one model pair per workgroup, on
+// given world poses and sizes of its two geoms.  Lane 0 stages them where the narrowphase reads
+// them (gxpos, gxquat, gsize of the pair's geoms in a shared Env) and calls the *_may_touch of
+// the pair's class as it stands; classes 0 and 1 have no cull (keep = 1).  info: keep, g1, g2,
+// class, type of g1, type of g2 (keep = -1, nothing else written: pair id out of range).
+__global__ void __launch_bounds__(64) k_midphase_test(DModel m, int n, const int* pair, const float* pos,
+                                                      const float* quat, const float* size, int* info,
+                                                      float* margin) {
+  __shared__ Env s;
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= n || lane != 0) return;
+  const int p = pair[i];
+  if ((unsigned)p >= (unsigned)m.npairall) { info[6 * i] = -1; return; }
+  const int g[2] = {MD(cp_g1, p), MD(cp_g2, p)};
+  for (int q = 0; q < 2; q++) {
+    for (int k = 0; k < 3; k++) { s.gxpos[g[q]][k] = pos[6 * i + 3 * q + k]; s.gsize[g[q]][k] = size[6 * i + 3 * q + k]; }
+    for (int k = 0; k < 4; k++) s.gxquat[g[q]][k] = quat[8 * i + 4 * q + k];
+  }
+  const int cls = MD(cp_class, p);
+  bool keep = true;
+  if (cls == 2) keep = capbox_may_touch(m, s, p);
+  else if (cls == 3) keep = boxbox_may_touch(m, s, p);
+  else if (cls == 4) keep = mpr_may_touch(m, s, p);
+  int* o = info + 6 * i;
+  o[0] = keep ? 1 : 0; o[1] = g[0]; o[2] = g[1]; o[3] = cls;
+  o[4] = MD(geom_type, g[0]); o[5] = MD(geom_type, g[1]);
+  margin[i] = MD(cp_margin, p);
+}
+
 __global__ void k_random_actions(int n, int nu, uint64_t seed, uint64_t step, uint64_t env_offset, float* out) {
   int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env >= n) return;
@@ -1019,6 +1048,17 @@ int aw_collide_test(aw_handle* h, int n, const int32_t* types, const float* pos,
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_collide_test, dim3(n), dim3(64), 0, st, h->m, n, types, pos, mat, size, margin, out, count, out64);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+int aw_midphase_test(aw_handle* h, int n, const int32_t* pair, const float* pos, const float* quat, const float* size,
+                     int32_t* info, float* margin, void* stream) {
+  if (!h || n <= 0 || !pair || !pos || !quat || !size || !info || !margin)
+    return fail(AW_EINVAL, "aw_midphase_test: bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_midphase_test, dim3(n), dim3(64), 0, st, h->m, n, pair, pos, quat, size, info, margin);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }

@@ -514,18 +514,23 @@ AW_DEV void c_box_box(const GV& A, const GV& B, float margin, Emit& e) {
       float du = pu[q2] - pu[q], dv = pv[q2] - pv[q];
 #pragma unroll
       for (int side = 0; side < 4; side++) {
+        // 0 < tt < 1 is decided on numerator and denominator, not on the quotient: the fp32 divide is
+        // not correctly rounded (x / x can come out below 1), and an incident corner lying exactly on
+        // the edge line (boxes stacked flush) would be emitted once more as a crossing
         float tt;
         if (side < 2) {
           float U = side == 0 ? hu : -hu;
           if (fabsf(du) < 1e-12f) continue;
-          tt = (U - pu[q]) / du;
-          if (!(tt > 0 && tt < 1)) continue;
+          const float nu = U - pu[q];
+          if (!(du > 0 ? (nu > 0 && nu < du) : (nu < 0 && nu > du))) continue;
+          tt = nu / du;
           if (fabsf(pv[q] + tt * dv) > hv) continue;
         } else {
           float V = side == 2 ? hv : -hv;
           if (fabsf(dv) < 1e-12f) continue;
-          tt = (V - pv[q]) / dv;
-          if (!(tt > 0 && tt < 1)) continue;
+          const float nu = V - pv[q];
+          if (!(dv > 0 ? (nu > 0 && nu < dv) : (nu < 0 && nu > dv))) continue;
+          tt = nu / dv;
           if (fabsf(pu[q] + tt * du) > hu) continue;
         }
         float X[3];
