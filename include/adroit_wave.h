@@ -525,6 +525,41 @@ int aw_render_cloud(aw_handle* h, const aw_view* views, int nviews, const float*
 int aw_cloud_fps(int n, int cap, const float* xyz, const int32_t* count, int npoints, float* out_xyz,
                  int32_t* out_idx, void* stream);
 
+/* Ray queries: mj_ray and the rangefinder sensor on the device.  A table of up to AW_MAX_RAYS rays,
+ * each attached to a body, is cast at every env's (or a subset's) current state in one launch: per ray
+ * the first render entry crossed and how far along the ray.
+ *   aw_set_rays: rays is a HOST array of nrays records; the call validates it, waits for the device
+ * (as aw_set_option does) and uploads it to a device table owned by the handle.  nrays == 0 drops the
+ * table.  pnt, vec: origin and direction in the frame of body `body` (0 = the world, used as given);
+ * the kernel composes pnt_w = xpos[b] + rot(xquat[b], pnt), vec_w = rot(xquat[b], vec) in fp32.  vec
+ * need not be unit.  xmax <= 0: no limit.  keep: bit e keeps render entry e (the primitive geoms, in
+ * aw_render_entries' order; bits at or above ngeom are ignored); mj_envs_amd/rays.py keep_mask
+ * builds it with mj_ray's elimination rules (geomgroup, flg_static, bodyexclude, alpha 0).
+ *   aw_cast_rays enqueues one launch on `stream`; it allocates nothing and does not wait.  env_ids /
+ * n_sel: as in aw_dynamics -- NULL (every env, n = N, n_sel ignored) or a DEVICE array of n_sel env
+ * ids, output row k is env env_ids[k]; an id outside [0, N) leaves its row untouched in both outputs.
+ * env_rays: NULL, or DEVICE [N][R][6] fp32 indexed by ENV id (R = the table's nrays): env e casts ray
+ * r from pnt, vec = env_rays[e][r][0..2], [3..5], expressed in the frame of rays[r].body; xmax, body
+ * and keep still come from record r.  The floats are not validated: a NaN or zero vec (or a
+ * non-finite pnt) is a miss, and a workgroup writes only its own row.
+ *   dist: DEVICE [n][R] fp32, the x >= 0 for which pnt_w + x vec_w is the first crossing with a kept
+ * entry (with a unit vec: metres) -- the smallest non-negative root (mju_rayGeom's rule), so a ray
+ * that starts inside a geom reports where it leaves it; the nearest entry wins, an exact tie goes to
+ * the lower entry.  -1 when nothing kept is crossed or x > xmax (xmax > 0).  entry: DEVICE [n][R]
+ * int32 or NULL, the render entry crossed, -1 on a miss.  Sites are never hit.  Nothing of the
+ * simulation state is written, and no appearance arrays are needed.
+ *   Two deviations from mj_ray: mesh geoms are absent (not available offline; the hand's primitive
+ * collision geoms are in the table), and planes are hit from both sides and are finite where their
+ * size is positive, as the depth renderer draws them (mj_ray: the front face of an infinite plane).
+ * AW_EINVAL, aw_set_rays: nrays outside 0..AW_MAX_RAYS, NULL rays with nrays > 0, a body outside
+ * [0, nbody), a zero or non-finite vec, a non-finite pnt or xmax.  aw_cast_rays: NULL h or dist, no
+ * ray table set, n_sel < 1 with env_ids given.  After either error every other call still works. */
+#define AW_MAX_RAYS 256
+typedef struct { float pnt[3], vec[3]; float xmax; int32_t body; uint64_t keep; } aw_ray_rec;  /* 40 bytes */
+int aw_set_rays(aw_handle* h, const aw_ray_rec* rays, int nrays);
+int aw_cast_rays(aw_handle* h, const int32_t* env_ids, int n_sel, const float* env_rays, float* dist,
+                 int32_t* entry, void* stream);
+
 /* On-device Gaussian MLP policy: mjrl gaussian_mlp.MLP as used by the
  * reference's DAPG baseline (algos/baselines.py:67-86, hidden_sizes=(32, 32)) -- two tanh
  * hidden layers of width `hidden` (32 or 64), in/out affine transforms, and with sample != 0

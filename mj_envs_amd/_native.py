@@ -109,6 +109,14 @@ class DynPoint(ctypes.Structure):
 class DynOut(ctypes.Structure):
     """aw_dyn_out: the device fp32 output buffers of aw_dynamics, NULL where not requested"""
     _fields_ = [(k, _vp) for k in DYN_OUTPUTS]
+
+
+# ray queries (include/adroit_wave.h aw_set_rays / aw_cast_rays): the table's capacity and aw_ray_rec as a
+# numpy structured type (40 bytes: pnt, vec, xmax, body, keep)
+AW_MAX_RAYS = 256
+RAY_DTYPE = np.dtype([("pnt", "<f4", (3,)), ("vec", "<f4", (3,)), ("xmax", "<f4"), ("body", "<i4"), ("keep", "<u8")])
+assert RAY_DTYPE.itemsize == 40
+
 # slots of a record vector [col | light | look] that aw_appearance_sample copies from ``lo``
 LIGHT_FLAG_SLOTS = (18, 20, 21)
 LOOK_FLAG_SLOT = 6
@@ -232,6 +240,10 @@ def load():
         L.aw_dynamics.argtypes = [_vp, _vp, ctypes.c_int, ctypes.POINTER(DynPoint), ctypes.c_int, _vp, _vp, _vp,
                                   ctypes.POINTER(DynOut), _vp]
         L.aw_dynamics.restype = ctypes.c_int
+    if hasattr(L, "aw_set_rays"):
+        L.aw_set_rays.argtypes = [_vp, _vp, ctypes.c_int]
+        L.aw_cast_rays.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]
+        L.aw_set_rays.restype = L.aw_cast_rays.restype = ctypes.c_int
     if hasattr(L, "aw_policy_mlp"):
         L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, _vp]
@@ -254,7 +266,7 @@ EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier",
            "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_dynamics", "aw_stage_profile", "aw_render_depth",
            "aw_render_rgb",
            "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_render_cloud", "aw_cloud_fps",
-           "aw_policy_mlp", "aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample",
+           "aw_set_rays", "aw_cast_rays", "aw_policy_mlp", "aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample",
            "aw_collide_test", "aw_midphase_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
@@ -869,6 +881,39 @@ class Sim:
         _check(load().aw_dynamics(self.h, _ptr(env_ids), n if n_sel is None else int(n_sel), arr,
                                   npt if npoints is None else int(npoints), _ptr(qpos), _ptr(qvel), _ptr(ctrl),
                                   ctypes.byref(c), _stream()))
+
+    def set_rays(self, records, nrays: Optional[int] = None):
+        """Upload the handle's ray table (include/adroit_wave.h aw_set_rays): ``records`` a host array
+        of ``RAY_DTYPE`` (mj_envs_amd/rays.py builds them), or None / empty to drop the table.  The
+        library validates the records (NativeError on a bad one) and waits for the device.  nrays:
+        the count handed to the library in place of the array's length."""
+        rec = None if records is None else np.ascontiguousarray(records, RAY_DTYPE).ravel()
+        n = (0 if rec is None else int(rec.size)) if nrays is None else int(nrays)
+        # a count the library refuses may be handed through; one it accepts must lie inside the array it reads
+        assert rec is None or n <= rec.size or n > AW_MAX_RAYS, "set_rays: nrays exceeds the records given"
+        _check(load().aw_set_rays(self.h, None if rec is None or rec.size == 0 else rec.ctypes.data, n))
+        self.nrays = n
+
+    def cast_rays(self, dist, entry=None, env_ids=None, env_rays=None, n_sel: Optional[int] = None):
+        """Cast the ray table at the selected envs' current state in one launch (include/adroit_wave.h
+        aw_cast_rays).  dist [n, R] (device, fp32): the x of the first crossing along pnt + x vec, -1
+        on a miss; entry [n, R] (device, int32) or None: the render entry crossed, -1 on a miss.
+        env_ids [n] (device, int32): output row k is env env_ids[k] (None: every env, n = n_envs).
+        env_rays [n_envs, R, 6] (device, fp32, indexed by env id): per-env pnt and vec in place of
+        the records' own.  n_sel: the count handed to the library with env_ids."""
+        import torch
+        n, R = self.n_envs, getattr(self, "nrays", 0)
+        if env_ids is not None:
+            _ids_ok(env_ids, "cast_rays: env_ids")
+            n = int(env_ids.shape[0])
+        for t, dt, what in ((dist, torch.float32, "dist"), (entry, torch.int32, "entry")):
+            assert t is None or (tuple(t.shape) == (n, R) and t.dtype == dt and t.is_contiguous() and t.is_cuda), \
+                f"cast_rays: {what} must be a device {dt} [{n}, {R}]"
+        assert env_rays is None or (tuple(env_rays.shape) == (self.n_envs, R, 6) and env_rays.dtype == torch.float32
+                                    and env_rays.is_contiguous() and env_rays.is_cuda), \
+            f"cast_rays: env_rays must be a device fp32 [{self.n_envs}, {R}, 6]"
+        _check(load().aw_cast_rays(self.h, _ptr(env_ids), n if n_sel is None else int(n_sel), _ptr(env_rays),
+                                   _ptr(dist), _ptr(entry), _stream()))
 
     def forward_dump(self, env: int, ctrl=None, wide: bool = False) -> dict:
         """one forward of env `env` (ctrl: raw controls or None = 0) and its internals; wide=True runs it

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -414,6 +415,7 @@ static void free_handle(aw_handle* h) {
   if (h->ddata) (void)hipFree(h->ddata);
   if (h->sensordata) (void)hipFree(h->sensordata);
   if (h->clone_scratch) (void)hipFree(h->clone_scratch);
+  if (h->rays) (void)hipFree(h->rays);
   if (h->app_bounds) (void)hipFree(h->app_bounds);
   delete h;
 }
@@ -839,6 +841,50 @@ int aw_dynamics(aw_handle* h, const int32_t* env_ids, int n_sel, const aw_dyn_po
   }
   HIPCHK(hipSetDevice(h->device));
   h->ops->dyn(h, env_ids, env_ids ? n_sel : h->nenv, pts, npoints, qpos, qvel, ctrl, *out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
+static_assert(sizeof(aw_ray_rec) == 40 && offsetof(aw_ray_rec, keep) == 32, "aw_ray_rec is 40 bytes");
+int aw_set_rays(aw_handle* h, const aw_ray_rec* rays, int nrays) {
+  if (!h) return fail(AW_EINVAL, "aw_set_rays: null");
+  if (nrays < 0 || nrays > AW_MAX_RAYS || (nrays > 0 && !rays))
+    return fail(AW_EINVAL, "aw_set_rays: nrays must be 0..AW_MAX_RAYS, with rays given");
+  // validated here, so that every index the kernel forms from the table is trusted
+  const unsigned long long all = h->m.nrgeom < 64 ? (1ull << h->m.nrgeom) - 1ull : ~0ull;
+  std::vector<aw_ray_rec> tab(rays, rays + nrays);
+  for (aw_ray_rec& r : tab) {
+    if (r.body < 0 || r.body >= h->m.nbody) return fail(AW_EINVAL, "aw_set_rays: a ray's body is not a body of the model");
+    bool fin = std::isfinite(r.xmax), zero = true;
+    for (int k = 0; k < 3; k++) {
+      fin = fin && std::isfinite(r.pnt[k]) && std::isfinite(r.vec[k]);
+      zero = zero && r.vec[k] == 0.f;
+    }
+    if (!fin || zero) return fail(AW_EINVAL, "aw_set_rays: pnt, vec and xmax must be finite and vec not zero");
+    r.keep &= all;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());   // casts already queued on any stream read the old table
+  if (nrays == 0) {
+    if (h->rays) HIPCHK(hipFree(h->rays));
+    h->rays = nullptr;
+    h->nrays = 0;
+    return AW_OK;
+  }
+  h->nrays = 0;   // no table while the upload can still fail
+  if (!h->rays) HIPCHK(hipMalloc(&h->rays, AW_MAX_RAYS * sizeof(aw_ray_rec)));
+  HIPCHK(hipMemcpy(h->rays, tab.data(), (size_t)nrays * sizeof(aw_ray_rec), hipMemcpyHostToDevice));
+  h->nrays = nrays;
+  return AW_OK;
+}
+
+int aw_cast_rays(aw_handle* h, const int32_t* env_ids, int n_sel, const float* env_rays, float* dist, int32_t* entry,
+                 void* stream) {
+  if (!h || !dist) return fail(AW_EINVAL, "aw_cast_rays: null handle or dist");
+  if (!h->rays || h->nrays < 1) return fail(AW_EINVAL, "aw_cast_rays: no ray table set (aw_set_rays)");
+  if (env_ids && n_sel < 1) return fail(AW_EINVAL, "aw_cast_rays: n_sel must be >= 1 with env_ids");
+  HIPCHK(hipSetDevice(h->device));
+  h->ops->rays(h, env_ids, env_ids ? n_sel : h->nenv, env_rays, dist, entry, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AW_OK;
 }

@@ -113,6 +113,8 @@ struct aw_handle {
   int shadows = 0;                            // nullptr: off) and cast shadows (has_appearance below)
   float* app_bounds = nullptr;          // aw_appearance_sample: the device copy of lo | hi, and what it holds
   std::vector<float> app_bounds_host;
+  void* rays = nullptr;          // aw_set_rays: the device ray table (AW_MAX_RAYS records of aw_ray_rec, allocated on
+  int nrays = 0;                 // the first call) and the number of rays it holds (0: no table; aw_cast_rays)
   void* clone_scratch = nullptr; // aw_clone_envs: the gathered source rows (state and episode counters of nenv
                                  // rows), allocated on the first call
 };
@@ -162,6 +164,7 @@ struct TaskOps {
                 float*, int32_t*, int32_t*, hipStream_t);
   void (*dyn)(aw_handle*, const int32_t*, int, const DynPts&, int, const float*, const float*, const float*,
               const aw_dyn_out&, hipStream_t);
+  void (*rays)(aw_handle*, const int32_t*, int, const float*, float*, int32_t*, hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 

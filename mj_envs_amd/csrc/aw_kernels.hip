@@ -1,7 +1,7 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
 // -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_set_state_ids, k_dump, k_depth, k_rgb, k_views,
-// k_views_app, k_labels, k_cloud, k_dyn (aw_dyn.h), k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide
+// k_views_app, k_labels, k_cloud, k_dyn (aw_dyn.h), k_rays (aw_rays.h), k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide
 // tier: k_step_wide, k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
 // env-step both tiers run is aw_step.h.  Written once: finish_forward (the tail of k_reset and the set-state kernels),
 // set_state_body (both set-state kernels), stage_pose / view_cam (the render kernels' prologue and per-view camera).
@@ -19,6 +19,7 @@
 #include "aw_step.h"
 #ifndef AW_WIDE
 #include "aw_dyn.h"   // k_dyn: the fast-tier unit only
+#include "aw_rays.h"  // k_rays: likewise
 #endif
 
 using namespace aw;
@@ -612,6 +613,73 @@ __global__ void __launch_bounds__(256) k_cloud(DModel m, DState st, int n, Views
   if (tid == 0) count[blockIdx.x] = base;
 }
 
+// ray queries (aw_cast_rays; aw_rays.h): output row blockIdx.x casts the handle's ray table at env
+// env_ids[blockIdx.x] (nullptr: env blockIdx.x); an id outside [0, n) is uniform over the block, which
+// leaves before its first barrier with its row untouched.  The block is 64 ceil(R / 64) threads and
+// thread r owns ray r: record r of the table (body, xmax and keep always; pnt and vec unless env_rays
+// gives the env's own six floats, indexed by ENV id), composed into the world from the body's frame
+// (body 0: as given).  A zero or non-finite vec, or a non-finite pnt, is a miss: nothing but floats
+// comes from env_rays, and the table's body was checked on the host, so every index is trusted.  The
+// direction is normalised after a scaling by its largest component (no under- or overflow of the
+// square), the crossing found in metres and divided by |vec|: dist is the x of pnt + x vec.
+// Stores: lane r writes dist[row][r] and entry[row][r], contiguous runs per wave, its own row only.
+template <int TASK>
+__global__ void __launch_bounds__(256) k_rays(DModel m, DState st, int n, const int* __restrict__ env_ids,
+                                              const RayRec* __restrict__ rays, int R,
+                                              const float* __restrict__ env_rays, float* dist, int* entry) {
+  constexpr int NV = Tree<TASK>::NV;
+  __shared__ Env s;
+  __shared__ RayGeoms rg;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int env = env_ids ? __builtin_amdgcn_readfirstlane(env_ids[blockIdx.x]) : (int)blockIdx.x;
+  if ((unsigned)env >= (unsigned)n) return;
+  if (tid < 64) stage_pose<NV>(m, s, st, env, lane);
+  __syncthreads();
+  ray_geoms(m, s, rg, tid, (int)blockDim.x);
+  __syncthreads();
+  const bool live = tid < R;
+  const RayRec& rec = rays[live ? tid : R - 1];
+  const int body = rec.body;
+  const float xmax = rec.xmax;
+  float pv[6];
+  if (env_rays) {
+    const float* er = env_rays + ((size_t)env * R + (live ? tid : R - 1)) * 6;
+    for (int k = 0; k < 6; k++) pv[k] = er[k];
+  } else {
+    for (int k = 0; k < 3; k++) { pv[k] = rec.pnt[k]; pv[3 + k] = rec.vec[k]; }
+  }
+  float o[3], v[3];
+  copy3(o, pv);
+  copy3(v, pv + 3);
+  if (body > 0) {
+    rotvq(o, pv, s.xquat[body]);
+    add3(o, o, s.xpos[body]);
+    rotvq(v, pv + 3, s.xquat[body]);
+  }
+  const float big = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
+  const float osum = fabsf(o[0]) + fabsf(o[1]) + fabsf(o[2]);
+  const bool ok = live && big > 0.f && big < 3.0e38f && osum < 3.0e38f;   // (a NaN fails every comparison)
+  float d[3] = {0.f, 0.f, 1.f}, len = 1.f;
+  if (ok) {
+    for (int k = 0; k < 3; k++) d[k] = v[k] / big;
+    const float nd = sqrtf(dot3(d, d));   // in [1, sqrt 3]
+    for (int k = 0; k < 3; k++) d[k] /= nd;
+    len = big * nd;
+  } else {
+    for (int k = 0; k < 3; k++) o[k] = 0.f;
+  }
+  const float tlim = xmax > 0.f ? 1.001f * (xmax * len) + 1.0e-6f : 3.0e38f;
+  int hit;
+  const float t = ray_nearest(rg, m.nrgeom, ok ? rec.keep : 0ull, o, d, tlim, hit);
+  float x = hit >= 0 ? t / len : -1.f;
+  if (!(x >= 0.f) || (xmax > 0.f && x > xmax)) { x = -1.f; hit = -1; }
+  if (live) {
+    const size_t i = (size_t)blockIdx.x * R + tid;
+    dist[i] = x;
+    if (entry) entry[i] = hit;
+  }
+}
+
 // Claim order for the next k_step launch (longest processing time first): per XCD class c (k_step's
 // env range [n c / 8, n (c + 1) / 8)) the envs are bucketed by their last env-step's shader cycles
 // on a quarter-octave scale and written costliest bucket first into perm (positions of the same
@@ -755,11 +823,18 @@ static void launch_dyn(aw_handle* h, const int32_t* env_ids, int grid, const Dyn
   hipLaunchKernelGGL((k_dyn<TASK>), dim3(grid), dim3(64), 0, st, h->m, h->st, h->nenv, env_ids, pts, npoints, qpos, qvel,
                      ctrl, out);
 }
+// grid: the output rows (the selected envs, or all of them); block: one thread per ray, whole waves
+template <int TASK>
+static void launch_rays(aw_handle* h, const int32_t* env_ids, int grid, const float* env_rays, float* dist,
+                        int32_t* entry, hipStream_t st) {
+  hipLaunchKernelGGL((k_rays<TASK>), dim3(grid), dim3(64 * ((h->nrays + 63) / 64)), 0, st, h->m, h->st, h->nenv, env_ids,
+                     (const RayRec*)h->rays, h->nrays, env_rays, dist, entry);
+}
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>, launch_set_ids<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
-                              launch_labels<TASK>, launch_cloud<TASK>, launch_dyn<TASK>};
+                              launch_labels<TASK>, launch_cloud<TASK>, launch_dyn<TASK>, launch_rays<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();

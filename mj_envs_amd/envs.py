@@ -57,7 +57,13 @@ class AdroitVecEnv:
 
     def __init__(self, env_id: str, num_envs: int, device: int = 0, variation_type: Optional[str] = None,
                  seed: int = 1, autoreset: bool = True, sensors: bool = False, data=False,
-                 max_contacts: int = 32):
+                 max_contacts: int = 32, rays=None):
+        """``rays`` (a ``rays.Rays`` table; None: off, and then nothing changes): after every ``step`` /
+        ``reset`` / ``set_state`` / ``clone`` one more launch casts the table and fills ``ray_dist``
+        [N, R], which ``step`` also returns as ``info["ray_dist"]``.  The rays are cast at the env's
+        CURRENT state -- the state the frames are rendered from (after an auto-reset: the new
+        episode's first state) --, not at the forward the obs comes from, which in a step lags the
+        state by one integration."""
         import torch
         # batched sim.data views (mj_envs_amd/data.py), opt-in: False, True (every group) or group names
         # out of "kin", "dyn", "contact"; checked before anything touches the GPU
@@ -102,6 +108,12 @@ class AdroitVecEnv:
         if self._data_groups:
             from .data import DataViews
             self._data = DataViews(self.model, s, self._data_groups, int(max_contacts))
+        # attached rays (mj_envs_amd/rays.py): cast after every state change into one device tensor
+        self._rays_key = None           # the bytes of the table the handle holds
+        self._los = {}                  # line_of_sight's segment tables by (K, filter)
+        self.rays = rays
+        if rays is not None:
+            self.ray_dist = torch.full((num_envs, len(rays)), -1.0, device=s.torch_device)
 
     @property
     def data(self):
@@ -129,6 +141,9 @@ class AdroitVecEnv:
     def _read_sensors(self):
         if self.sensors:
             self.sim.sensordata(self._sensordata)
+        if self.rays is not None:       # every caller has just changed the state: cast the attached rays at it
+            self._upload_rays(self.rays)
+            self.sim.cast_rays(self.ray_dist)
 
     # --- episode control -------------------------------------------------------------------
     def reset(self, mask=None, params=None, seed: Optional[int] = None):
@@ -150,9 +165,11 @@ class AdroitVecEnv:
         self.sim.status(last=self._status)
         info = {"goal_achieved": self.goal.bool(), "terminal_obs": self.terminal_obs,
                 "status": self._status}    # AW_ST_* flags of this step (NaN reset, overflow)
+        self._read_sensors()
         if self.sensors:
-            self._read_sensors()
             info["sensordata"] = self._sensordata
+        if self.rays is not None:
+            info["ray_dist"] = self.ray_dist
         return self.obs, self.reward, terminated, truncated, info
 
     def random_actions(self, out, step: int, seed: int = 0):
@@ -374,6 +391,62 @@ class AdroitVecEnv:
             return out, count
         index = torch.where(idx >= 0, torch.gather(pix, 1, idx.clamp(min=0).long()), idx)
         return out, count, index
+
+    # --- ray queries (mj_envs_amd/rays.py) -------------------------------------------------------
+    def _upload_rays(self, rays):
+        """the handle holds one table: upload ``rays`` unless it is the set last uploaded"""
+        key = rays.key()
+        if key != self._rays_key:
+            if len(rays) < 1:
+                raise ValueError("raycast: an empty ray table")
+            self.sim.set_rays(rays.records)
+            self._rays_key = key
+
+    def raycast(self, rays, env_ids=None, env_rays=None, entry: bool = True):
+        """Cast the table ``rays`` (``rays.Rays``: ``body_rays``, ``rangefinder``, ``fan``, ``segments``,
+        ``concat``) at the current state of every env, or of ``env_ids`` (a list, a numpy array or a
+        device int32 tensor; ids may repeat), in one launch (``aw_cast_rays``): MuJoCo's ``mj_ray`` per
+        ray.  ``env_rays`` [N, R, 6] (device fp32, indexed by env id): per-env ``pnt``, ``vec`` in the
+        frame of each ray's body, in place of the table's own (range limits, bodies and filters stay
+        the table's; a NaN or zero ``vec`` is a miss).  Returns ``rays.RayHits``: ``dist`` [n, R] (the x
+        of ``pnt + x vec``, -1 on a miss), ``hit``, and with ``entry`` the render entry, ``geom_id`` and
+        ``body_id``.  The table is uploaded when it is not the one last uploaded to this handle
+        (which waits for the device); the cast itself allocates only its outputs and does not wait."""
+        import torch
+        from .rays import RayHits
+        self._upload_rays(rays)
+        ids = None if env_ids is None else self._ids(env_ids, self.num_envs, "env_ids", distinct=False)
+        n, R = self.num_envs if ids is None else int(ids.shape[0]), len(rays)
+        if env_rays is not None:
+            if tuple(env_rays.shape) != (self.num_envs, R, 6):
+                raise ValueError(f"raycast: env_rays must be [{self.num_envs}, {R}, 6], not {tuple(env_rays.shape)}")
+            env_rays = env_rays.to(torch.float32).contiguous()
+        dist = self.sim.empty(n, R)
+        ent = self.sim.empty(n, R, dtype=torch.int32) if entry else None
+        if ids is not None:             # (a row whose id a device tensor puts out of range stays a miss)
+            dist.fill_(-1.0)
+            if ent is not None:
+                ent.fill_(-1)
+        self.sim.cast_rays(dist, ent, env_ids=ids, env_rays=env_rays)
+        return RayHits(rays, dist, ent)
+
+    def line_of_sight(self, a, b, **filter):
+        """Is the segment from ``a`` to ``b`` blocked?  ``a``, ``b``: [N, K, 3] device tensors in the
+        world frame (site or body positions from ``data`` / ``dynamics``, targets ...); ``filter``: the
+        keywords of ``rays.keep_mask`` (``bodyexclude=``, ``bodies=`` ...).  One launch over
+        ``rays.segments``.  Returns ``(occluded [N, K] bool, entry [N, K] int32)``: a kept geom is
+        crossed at ``a + x (b - a)`` with 0 <= x < 1, and the first such entry (-1: none)."""
+        import torch
+        from .rays import segments
+        if a.shape != b.shape or a.dim() != 3 or a.shape[0] != self.num_envs or a.shape[2] != 3:
+            raise ValueError(f"line_of_sight: a and b are [{self.num_envs}, K, 3]")
+        k = int(a.shape[1])
+        key = (k, tuple(sorted((n, repr(v)) for n, v in filter.items())))
+        if key not in self._los:
+            self._los[key] = segments(self.model, k, **filter)
+        hits = self.raycast(self._los[key], env_rays=torch.cat([a, b - a], dim=-1))
+        occluded = (hits.dist >= 0) & (hits.dist < 1)
+        return occluded, torch.where(occluded, hits.entry, torch.full_like(hits.entry, -1))
 
     # --- state -----------------------------------------------------------------------------
     def _ids(self, ids, n: int, name: str, distinct: bool = True):
@@ -618,6 +691,20 @@ class _AdroitEnv(_reference_base()):
             ctrl = torch.as_tensor(self.vec.act_mid, device=self._dev) + a * torch.as_tensor(self.vec.act_rng,
                                                                                                device=self._dev)
         return EnvDynamics(self.vec, ctrl)
+
+    def ray(self, pnt, vec, geomgroup=None, flg_static=1, bodyexclude=-1):
+        """``mj_ray(m, d, pnt, vec, geomgroup, flg_static, bodyexclude, geomid)`` at the current state:
+        ``(dist, geomid)`` of the first geom the world-frame ray ``pnt + x vec`` crosses -- ``dist`` is
+        that x (metres for a unit ``vec``) --, ``(-1.0, -1)`` when it crosses none.  ``geomgroup``: 6
+        flags or None, ``flg_static`` 0 drops the geoms of static bodies, ``bodyexclude``: a body id
+        (-1: none).  Deviations from MuJoCo (mj_envs_amd/rays.py): no mesh geoms; planes two-sided
+        and finite."""
+        from .rays import body_rays
+        r = body_rays(self.model, 0, pnt, vec, geomgroup=geomgroup, flg_static=bool(flg_static), bodyexclude=bodyexclude)
+        if len(r) != 1:
+            raise ValueError("ray: one pnt and one vec")
+        hits = self.vec.raycast(r)
+        return float(hits.dist[0, 0]), int(hits.geom_id[0, 0])
 
     def _params(self) -> np.ndarray:
         return self.vec.get_state()["params"][0].cpu().numpy().astype(np.float64)
