@@ -4,6 +4,9 @@ The product path: every compute call goes to the HIP library.  There is no CPU f
 if the library is missing or cannot be loaded, ``load()`` raises.  Device memory is managed
 with torch (``torch.cuda`` tensors are HIP allocations on ROCm); pointers and the current
 stream are passed through as plain integers.
+
+The boundary is stated once: ``ABI`` holds the return and argument types of every exported
+function, ``_dev`` is the one check of a device tensor before its address crosses it.
 """
 from __future__ import annotations
 
@@ -60,7 +63,7 @@ DATA_BUFFERS = {AW_DATA_KIN: ("xpos", "xquat", "site_xpos"), AW_DATA_DYN: ("qacc
                 AW_DATA_CONTACT: ("contact",)}
 
 _lib = None
-_vp = ctypes.c_void_p
+_i, _u64, _sz, _vp, _P = ctypes.c_int, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER
 
 
 class DataBufs(ctypes.Structure):
@@ -69,13 +72,14 @@ class DataBufs(ctypes.Structure):
 
 
 AW_MAX_VIEWS = 4
+AW_CAM_FLOATS = 17           # floats of a host camera record (mj_envs_amd/render.py)
 AW_CLOUD_MAXCAND = 8192      # candidate slots per row (aw_render_cloud, aw_cloud_fps)
 AW_FPS_MAXPOINTS = 1024      # sampled points per row (aw_cloud_fps)
 
 
 class View(ctypes.Structure):
     """aw_view: a camera record in the frame of a body (0: the world)"""
-    _fields_ = [("rec", ctypes.c_float * 17), ("body", ctypes.c_int32)]
+    _fields_ = [("rec", ctypes.c_float * AW_CAM_FLOATS), ("body", ctypes.c_int32)]
 
 
 class AppearanceBufs(ctypes.Structure):
@@ -121,6 +125,60 @@ assert RAY_DTYPE.itemsize == 40
 LIGHT_FLAG_SLOTS = (18, 20, 21)
 LOOK_FLAG_SLOT = 6
 
+# Every exported function of include/adroit_wave.h, in the header's order: name -> (restype, argtypes).
+# The only statement of the binding's types (tests/test_native_abi.py holds it to the header's
+# prototypes): a new entry point is one line here and one method below.
+ABI = {
+    "aw_create": (_i, [_vp, _sz, _i, _i, _P(_vp)]),
+    "aw_destroy": (_i, [_vp]),
+    "aw_dims": (_i, [_vp, _P(_i)]),
+    "aw_set_option": (_i, [_vp, _i, _i, _i]),
+    "aw_set_tier": (_i, [_vp, _i]),
+    "aw_set_fault": (_i, [_vp, _i, _i]),
+    "aw_set_sensors": (_i, [_vp, _i]),
+    "aw_sensor_count": (_i, [_vp]),
+    "aw_sensordata": (_i, [_vp, _vp, _vp]),
+    "aw_set_data": (_i, [_vp, _i, _i, _P(DataBufs)]),
+    "aw_reset": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "aw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u64, _vp]),
+    "aw_random_actions": (_i, [_vp, _u64, _u64, _vp, _vp]),
+    "aw_set_env_offset": (_i, [_vp, _u64]),
+    "aw_get_state": (_i, [_vp] * 6),
+    "aw_set_state": (_i, [_vp] * 7),
+    "aw_set_state_ids": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "aw_get_state_ids": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "aw_clone_envs": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "aw_status": (_i, [_vp] * 4),
+    "aw_clear_status": (_i, [_vp, _vp]),
+    "aw_episode_stats": (_i, [_vp] * 6),
+    "aw_episode_totals": (_i, [_vp] * 5),
+    "aw_set_episode_totals": (_i, [_vp] * 5),
+    "aw_get_episode": (_i, [_vp] * 6),
+    "aw_set_episode": (_i, [_vp] * 6),
+    "aw_task_eval": (_i, [_vp, _i] + [_vp] * 11),
+    "aw_forward_dump": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "aw_forward_dump_wide": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "aw_dynamics": (_i, [_vp, _vp, _i, _P(DynPoint), _i, _vp, _vp, _vp, _P(DynOut), _vp]),
+    "aw_render_depth": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "aw_render_rgb": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "aw_render_views": (_i, [_vp, _P(View), _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "aw_set_appearance": (_i, [_vp, _P(AppearanceBufs), _i]),
+    "aw_appearance_defaults": (_i, [_vp, _vp, _vp, _P(_i)]),
+    "aw_appearance_sample": (_i, [_vp, _vp, _vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "aw_render_entries": (_i, [_vp, _P(_i), _P(_i)]),
+    "aw_render_labels": (_i, [_vp, _P(View), _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "aw_render_cloud": (_i, [_vp, _P(View), _i, _vp, _vp, _i, _vp, _vp] + [_i] * 5 + [_vp] * 4),
+    "aw_cloud_fps": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "aw_set_rays": (_i, [_vp, _vp, _i]),
+    "aw_cast_rays": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "aw_policy_mlp": (_i, [_i] * 4 + [_vp, _vp, _vp, _i, _u64, _u64, _u64, _vp]),
+    "aw_collide_test": (_i, [_vp, _i] + [_vp] * 9),
+    "aw_midphase_test": (_i, [_vp, _i] + [_vp] * 7),
+    "aw_stage_profile": (_i, [_vp, _i]),
+    "aw_last_error": (ctypes.c_char_p, []),
+}
+EXPORTS = tuple(ABI)
+
 
 def data_groups(data) -> int:
     """AW_DATA_* mask of ``data``: False / None -> 0, True -> every group, a group name or an
@@ -147,127 +205,26 @@ class NativeError(RuntimeError):
 
 
 def load():
-    """Load libadroit_hip.so (raises if absent: the HIP path is the only path)."""
+    """Load libadroit_hip.so (raises if absent: the HIP path is the only path) and give every
+    function of ``ABI`` its types.  A symbol the library lacks: with AW_LIB set (a diagnostic
+    build, possibly of an older revision) it is skipped, and calling it raises AttributeError;
+    without AW_LIB (the product library) ``load()`` raises NativeError naming every missing one."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise NativeError(f"{LIB_PATH} not built; run `python -c 'import __graft_entry__ as g; g.build()'`")
     L = ctypes.CDLL(LIB_PATH)
-    L.aw_last_error.restype = ctypes.c_char_p
-    L.aw_create.argtypes = [_vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]
-    L.aw_destroy.argtypes = [_vp]
-    L.aw_dims.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
-    L.aw_set_option.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.aw_reset.argtypes = [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]
-    L.aw_step.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64, _vp]
-    L.aw_random_actions.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]
-    L.aw_set_env_offset.argtypes = [_vp, ctypes.c_uint64]
-    L.aw_set_tier.argtypes = [_vp, ctypes.c_int]
-    if hasattr(L, "aw_set_sensors"):
-        L.aw_set_sensors.argtypes = [_vp, ctypes.c_int]
-        L.aw_sensor_count.argtypes = [_vp]
-        L.aw_sensordata.argtypes = [_vp, _vp, _vp]
-        for f in ("aw_set_sensors", "aw_sensor_count", "aw_sensordata"):
-            getattr(L, f).restype = ctypes.c_int
-    if hasattr(L, "aw_set_data"):
-        L.aw_set_data.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DataBufs)]
-        L.aw_set_data.restype = ctypes.c_int
-    if hasattr(L, "aw_forward_dump_wide"):
-        L.aw_forward_dump_wide.argtypes = [_vp, ctypes.c_int, _vp, _vp, _vp]
-        L.aw_forward_dump_wide.restype = ctypes.c_int
-    if hasattr(L, "aw_set_fault"):
-        L.aw_set_fault.argtypes = [_vp, ctypes.c_int, ctypes.c_int]
-        L.aw_set_fault.restype = ctypes.c_int
-    L.aw_clear_status.argtypes = [_vp, _vp]
-    L.aw_episode_totals.argtypes = [_vp, _vp, _vp, _vp, _vp]
-    L.aw_get_episode.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
-    L.aw_set_episode.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
-    L.aw_get_state.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
-    L.aw_set_state.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.aw_status.argtypes = [_vp, _vp, _vp, _vp]
-    L.aw_episode_stats.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
-    L.aw_task_eval.argtypes = [_vp, ctypes.c_int] + [_vp] * 10 + [_vp]
-    L.aw_forward_dump.argtypes = [_vp, ctypes.c_int, _vp, _vp, _vp]
-    L.aw_stage_profile.argtypes = [_vp, ctypes.c_int]
-    L.aw_collide_test.argtypes = [_vp, ctypes.c_int] + [_vp] * 9
-    L.aw_collide_test.restype = ctypes.c_int
-    if hasattr(L, "aw_midphase_test"):
-        L.aw_midphase_test.argtypes = [_vp, ctypes.c_int] + [_vp] * 7
-        L.aw_midphase_test.restype = ctypes.c_int
-    # (diagnostic builds of older revisions, selected with AW_LIB, may lack the newer entry points;
-    # calling one of those then raises AttributeError)
-    if hasattr(L, "aw_set_episode_totals"):
-        L.aw_set_episode_totals.argtypes = [_vp, _vp, _vp, _vp, _vp]
-        L.aw_set_episode_totals.restype = ctypes.c_int
-    if hasattr(L, "aw_render_depth"):
-        L.aw_render_depth.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]
-        L.aw_render_depth.restype = ctypes.c_int
-    if hasattr(L, "aw_render_rgb"):
-        L.aw_render_rgb.argtypes = [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]
-        L.aw_render_rgb.restype = ctypes.c_int
-    if hasattr(L, "aw_render_views"):
-        L.aw_render_views.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, _vp, _vp, _vp]
-        L.aw_render_views.restype = ctypes.c_int
-    if hasattr(L, "aw_render_labels"):
-        L.aw_render_entries.argtypes = [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        L.aw_render_entries.restype = ctypes.c_int
-        L.aw_render_labels.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
-                                       ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]
-        L.aw_render_labels.restype = ctypes.c_int
-    if hasattr(L, "aw_render_cloud"):
-        L.aw_render_cloud.argtypes = [_vp, ctypes.POINTER(View), ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp] + \
-            [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp]
-        L.aw_render_cloud.restype = ctypes.c_int
-        L.aw_cloud_fps.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]
-        L.aw_cloud_fps.restype = ctypes.c_int
-    if hasattr(L, "aw_set_appearance"):
-        L.aw_set_appearance.argtypes = [_vp, ctypes.POINTER(AppearanceBufs), ctypes.c_int]
-        L.aw_appearance_defaults.argtypes = [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_int)]
-        L.aw_appearance_sample.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
-                                           _vp, _vp, _vp, _vp]
-        for f in ("aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample"):
-            getattr(L, f).restype = ctypes.c_int
-    if hasattr(L, "aw_set_state_ids"):
-        L.aw_set_state_ids.argtypes = [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
-                                       _vp, _vp]
-        L.aw_get_state_ids.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]
-        L.aw_clone_envs.argtypes = [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]
-        for f in ("aw_set_state_ids", "aw_get_state_ids", "aw_clone_envs"):
-            getattr(L, f).restype = ctypes.c_int
-    if hasattr(L, "aw_dynamics"):
-        L.aw_dynamics.argtypes = [_vp, _vp, ctypes.c_int, ctypes.POINTER(DynPoint), ctypes.c_int, _vp, _vp, _vp,
-                                  ctypes.POINTER(DynOut), _vp]
-        L.aw_dynamics.restype = ctypes.c_int
-    if hasattr(L, "aw_set_rays"):
-        L.aw_set_rays.argtypes = [_vp, _vp, ctypes.c_int]
-        L.aw_cast_rays.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]
-        L.aw_set_rays.restype = L.aw_cast_rays.restype = ctypes.c_int
-    if hasattr(L, "aw_policy_mlp"):
-        L.aw_policy_mlp.argtypes = [ctypes.c_int] * 4 + [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint64,
-                                                         ctypes.c_uint64, ctypes.c_uint64, _vp]
-        L.aw_policy_mlp.restype = ctypes.c_int
-    for f in ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_reset", "aw_step",
-              "aw_random_actions", "aw_get_state", "aw_set_state", "aw_status", "aw_episode_stats",
-              "aw_task_eval", "aw_forward_dump", "aw_stage_profile", "aw_set_env_offset", "aw_clear_status",
-              "aw_episode_totals", "aw_get_episode", "aw_set_episode", "aw_set_tier"):
-        getattr(L, f).restype = ctypes.c_int
+    fns = {name: getattr(L, name, None) for name in ABI}
+    missing = [name for name, fn in fns.items() if fn is None]
+    if missing and not os.environ.get("AW_LIB"):
+        raise NativeError(f"{LIB_PATH} lacks {', '.join(missing)}; rebuild it")
+    for name, fn in fns.items():
+        if fn is not None:
+            fn.restype, fn.argtypes = ABI[name]
     _lib = L
     return L
 
-
-EXPORTS = ("aw_create", "aw_destroy", "aw_dims", "aw_set_option", "aw_set_tier", "aw_set_fault", "aw_reset", "aw_step",
-           "aw_set_sensors", "aw_sensor_count", "aw_sensordata", "aw_set_data",
-           "aw_random_actions", "aw_set_env_offset", "aw_get_state", "aw_set_state", "aw_set_state_ids",
-           "aw_get_state_ids", "aw_clone_envs", "aw_status",
-           "aw_clear_status", "aw_episode_stats", "aw_episode_totals", "aw_set_episode_totals", "aw_get_episode",
-           "aw_set_episode",
-           "aw_task_eval", "aw_forward_dump", "aw_forward_dump_wide", "aw_dynamics", "aw_stage_profile", "aw_render_depth",
-           "aw_render_rgb",
-           "aw_render_views", "aw_render_entries", "aw_render_labels", "aw_render_cloud", "aw_cloud_fps",
-           "aw_set_rays", "aw_cast_rays", "aw_policy_mlp", "aw_set_appearance", "aw_appearance_defaults", "aw_appearance_sample",
-           "aw_collide_test", "aw_midphase_test", "aw_last_error")
 
 STAGES = ("pre", "kinematics", "collision", "com_crb", "rne_smooth_solve", "constraints", "newton",
           "noslip", "jt_touch", "euler", "task_obs", "reset", "checks")
@@ -350,10 +307,49 @@ def check_ids(ids, n: int, name: str = "env_ids", distinct: bool = True) -> np.n
     return np.ascontiguousarray(a, np.int32)
 
 
-def _ids_ok(t, what: str):
-    import torch
-    assert t.dim() == 1 and t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda, \
-        f"{what} must be a device int32 vector"
+def _require(ok, msg: str):
+    """an argument check that ``python -O`` does not remove"""
+    if not ok:
+        raise AssertionError(msg)
+
+
+def _dev(t, what: str, dtype, shape, optional: bool = True):
+    """The check of a tensor whose address goes to the library: ``t`` must be on the device,
+    contiguous, of ``dtype`` and exactly of ``shape`` (a None in it leaves that dimension free;
+    ``shape`` None: any shape); None passes only where ``optional``.  Returns ``t``; AssertionError
+    ``"<call>: <name> must be a device <dtype> <shape>"`` otherwise (``what``: ``"<call>: <name>"``)."""
+    if t is None and optional:
+        return None
+    ok = t is not None and getattr(t, "is_cuda", False) and t.dtype == dtype and t.is_contiguous()
+    if ok and shape is not None:
+        ok = t.dim() == len(shape) and all(w is None or int(d) == int(w) for d, w in zip(t.shape, shape))
+    if not ok:
+        dims = "" if shape is None else " [" + ", ".join("*" if w is None else str(int(w)) for w in shape) + "]"
+        raise AssertionError(f"{what} must be a device {dtype}{dims}")
+    return t
+
+
+def _record(x, n: int, what: str):
+    """a host fp32 record of exactly ``n`` floats (a camera, look or box record) as a flat array
+    whose address goes to the library; None stays None"""
+    if x is None:
+        return None
+    a = np.ascontiguousarray(x, np.float32).ravel()
+    _require(a.size == n, f"{what} has {n} floats")
+    return a
+
+
+def _host_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _views_arg(views, call: str):
+    """(aw_view array, nviews) of a list of (camera record, body) pairs"""
+    arr = (View * max(len(views), 1))()
+    for k, (rec, body) in enumerate(views):
+        arr[k].rec[:] = _record(rec, AW_CAM_FLOATS, f"{call}: a camera record").tolist()
+        arr[k].body = int(body)
+    return arr, len(views)
 
 
 def cloud_fps(xyz, count, out_xyz, out_idx=None, cap: Optional[int] = None, npoints: Optional[int] = None):
@@ -364,27 +360,24 @@ def cloud_fps(xyz, count, out_xyz, out_idx=None, cap: Optional[int] = None, npoi
     rows shorter than P repeat cyclically, an empty row is zeros / -1.  cap, npoints: handed to the
     library in place of the tensors' dimensions."""
     import torch
-    for t, what in ((xyz, "xyz"), (out_xyz, "out_xyz")):
-        assert t is None or (t.dim() == 3 and t.shape[2] == 3 and t.dtype == torch.float32 and t.is_contiguous()
-                             and t.is_cuda), f"cloud_fps: {what} must be a device fp32 [n, ., 3]"
+    _dev(xyz, "cloud_fps: xyz", torch.float32, (None, None, 3))
+    _dev(out_xyz, "cloud_fps: out_xyz", torch.float32, (None, None, 3))
+    _dev(count, "cloud_fps: count", torch.int32, (None,))
     n = int(count.shape[0]) if count is not None else int(xyz.shape[0])
     if cap is None:
         cap = int(xyz.shape[1])
     if npoints is None:
         npoints = int(out_xyz.shape[1])
+    # a count the library refuses may be handed through; one it accepts is the row stride it works with
     if xyz is not None:
-        assert xyz.shape[0] == n and (cap == xyz.shape[1] or not 1 <= cap <= AW_CLOUD_MAXCAND), \
-            "cloud_fps: cap is xyz's second dimension"
+        _require(xyz.shape[0] == n and (cap == xyz.shape[1] or not 1 <= cap <= AW_CLOUD_MAXCAND),
+                 "cloud_fps: cap is xyz's second dimension")
     if out_xyz is not None:
-        assert out_xyz.shape[0] == n and (npoints == out_xyz.shape[1] or not 1 <= npoints <= AW_FPS_MAXPOINTS), \
-            "cloud_fps: npoints is out_xyz's second dimension"
-    if count is not None:
-        assert count.dim() == 1 and count.dtype == torch.int32 and count.is_contiguous() and count.is_cuda, \
-            "cloud_fps: count must be a device int32 vector"
+        _require(out_xyz.shape[0] == n and (npoints == out_xyz.shape[1] or not 1 <= npoints <= AW_FPS_MAXPOINTS),
+                 "cloud_fps: npoints is out_xyz's second dimension")
     if out_idx is not None:
-        assert out_xyz is not None and tuple(out_idx.shape) == tuple(out_xyz.shape[:2]) and \
-            out_idx.dtype == torch.int32 and out_idx.is_contiguous() and out_idx.is_cuda, \
-            "cloud_fps: out_idx must be a device int32 [n, P]"
+        _require(out_xyz is not None, "cloud_fps: out_idx needs out_xyz")
+        _dev(out_idx, "cloud_fps: out_idx", torch.int32, tuple(out_xyz.shape[:2]))
     _check(load().aw_cloud_fps(n, int(cap), _ptr(xyz), _ptr(count), int(npoints), _ptr(out_xyz), _ptr(out_idx),
                                _stream()))
 
@@ -452,8 +445,7 @@ class Sim:
         """copy the sensor buffer into out [n_envs, nsensordata] (device, fp32); raises while
         sensors are off"""
         import torch
-        assert tuple(out.shape) == (self.n_envs, self.nsensordata) and out.dtype == torch.float32 and \
-            out.is_contiguous(), "sensordata: out must be fp32 [n_envs, nsensordata]"
+        _dev(out, "sensordata: out", torch.float32, (self.n_envs, self.nsensordata), optional=False)
         _check(load().aw_sensordata(self.h, _ptr(out), _stream()))
         return out
 
@@ -482,8 +474,8 @@ class Sim:
                     dt = torch.int32 if k == "counts" else torch.float32
                     t = bufs[k] if bufs and k in bufs else torch.zeros(shapes[k], dtype=dt, device=self.torch_device)
                     need = int(np.prod(shapes[k]))
-                    assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() >= need, \
-                        f"set_data: {k} must be a contiguous {dt} device tensor of >= {need} elements"
+                    _dev(t, f"set_data: {k}", dt, None, optional=False)
+                    _require(t.numel() >= need, f"set_data: {k} must hold >= {need} elements")
                     out[k] = t
                     setattr(c, k, t.data_ptr())
         _check(load().aw_set_data(self.h, g, K, ctypes.byref(c)))
@@ -514,13 +506,19 @@ class Sim:
         _check(load().aw_set_state(self.h, _ptr(qpos), _ptr(qvel), _ptr(warm), _ptr(params), _ptr(obs),
                                    _stream()))
 
-    def _state_rows(self, what, n, qpos, qvel, warm, params):
-        """the state arrays of the indexed calls: device fp32 [n, nq | nv | nv | nparam] or None"""
+    def _rows(self, call: str, n: int, **arrays):
+        """the per-row arrays of a call: device fp32 [n, nq | nv | nv | nparam | nu] or None"""
         import torch
-        for t, w, k in ((qpos, self.nq, "qpos"), (qvel, self.nv, "qvel"), (warm, self.nv, "warm"),
-                        (params, self.nparam, "params")):
-            assert t is None or (tuple(t.shape) == (n, w) and t.dtype == torch.float32 and t.is_contiguous()
-                                 and t.is_cuda), f"{what}: {k} must be a device fp32 [{n}, {w}]"
+        width = dict(qpos=self.nq, qvel=self.nv, warm=self.nv, params=self.nparam, ctrl=self.nu)
+        for k, t in arrays.items():
+            _dev(t, f"{call}: {k}", torch.float32, (n, width[k]))
+
+    def _n_sel(self, call: str, env_ids) -> int:
+        """rows of a call that selects envs with ``env_ids`` (a device int32 vector; None: every env)"""
+        import torch
+        if _dev(env_ids, f"{call}: env_ids", torch.int32, (None,)) is None:
+            return self.n_envs
+        return int(env_ids.shape[0])
 
     def set_state_ids(self, env_ids, rows=None, n_rows: Optional[int] = None, qpos=None, qvel=None, warm=None,
                       params=None, reset_episode: bool = False, obs=None):
@@ -528,25 +526,25 @@ class Sim:
         its forward (include/adroit_wave.h aw_set_state_ids).  env_ids, rows: device int32 vectors, not
         validated (the library skips ids and rows out of range; env_ids must be distinct).  obs:
         [n_envs, obs_dim], indexed by env id; only the selected envs' rows are written."""
+        import torch
         given = [t for t in (qpos, qvel, warm, params) if t is not None]
-        _ids_ok(env_ids, "set_state_ids: env_ids")
+        _dev(env_ids, "set_state_ids: env_ids", torch.int32, (None,), optional=False)
         n_sel = int(env_ids.shape[0])
-        if rows is not None:
-            _ids_ok(rows, "set_state_ids: rows")
-            assert int(rows.shape[0]) == n_sel, "set_state_ids: one row per env id"
+        _dev(rows, "set_state_ids: rows", torch.int32, (n_sel,))
         if n_rows is None:
             n_rows = int(given[0].shape[0]) if given else n_sel
-        self._state_rows("set_state_ids", n_rows, qpos, qvel, warm, params)
-        assert obs is None or tuple(obs.shape) == (self.n_envs, self.obs_dim), "set_state_ids: obs is [n_envs, obs_dim]"
+        self._rows("set_state_ids", n_rows, qpos=qpos, qvel=qvel, warm=warm, params=params)
+        _dev(obs, "set_state_ids: obs", torch.float32, (self.n_envs, self.obs_dim))
         _check(load().aw_set_state_ids(self.h, _ptr(env_ids), n_sel, _ptr(rows), int(n_rows), _ptr(qpos), _ptr(qvel),
                                        _ptr(warm), _ptr(params), int(bool(reset_episode)), _ptr(obs), _stream()))
 
     def get_state_ids(self, env_ids, qpos=None, qvel=None, warm=None, params=None):
         """row k of the given [n_sel, ...] arrays receives env env_ids[k] (device int32; an id out of
         range leaves its row as it was): include/adroit_wave.h aw_get_state_ids"""
-        _ids_ok(env_ids, "get_state_ids: env_ids")
+        import torch
+        _dev(env_ids, "get_state_ids: env_ids", torch.int32, (None,), optional=False)
         n_sel = int(env_ids.shape[0])
-        self._state_rows("get_state_ids", n_sel, qpos, qvel, warm, params)
+        self._rows("get_state_ids", n_sel, qpos=qpos, qvel=qvel, warm=warm, params=params)
         _check(load().aw_get_state_ids(self.h, _ptr(env_ids), n_sel, _ptr(qpos), _ptr(qvel), _ptr(warm), _ptr(params),
                                        _stream()))
 
@@ -554,12 +552,13 @@ class Sim:
         """env dst_ids[k] becomes a copy of env src_ids[k] (device int32 vectors; every read before any
         write; dst_ids distinct), then the forward of the dst envs: include/adroit_wave.h aw_clone_envs.
         The first call allocates the handle's scratch block."""
-        _ids_ok(src_ids, "clone_envs: src_ids")
-        _ids_ok(dst_ids, "clone_envs: dst_ids")
-        assert src_ids.shape == dst_ids.shape, "clone_envs: one source per destination"
-        assert obs is None or tuple(obs.shape) == (self.n_envs, self.obs_dim), "clone_envs: obs is [n_envs, obs_dim]"
-        _check(load().aw_clone_envs(self.h, _ptr(src_ids), _ptr(dst_ids), int(src_ids.shape[0]), int(bool(episode)),
-                                    _ptr(obs), _stream()))
+        import torch
+        _dev(src_ids, "clone_envs: src_ids", torch.int32, (None,), optional=False)
+        n = int(src_ids.shape[0])
+        _dev(dst_ids, "clone_envs: dst_ids", torch.int32, (n,), optional=False)
+        _dev(obs, "clone_envs: obs", torch.float32, (self.n_envs, self.obs_dim))
+        _check(load().aw_clone_envs(self.h, _ptr(src_ids), _ptr(dst_ids), n, int(bool(episode)), _ptr(obs),
+                                    _stream()))
 
     def status(self, last=None, sticky=None):
         """per-env flags (ST_*): of the last step (last) / OR since create or clear_status (sticky)"""
@@ -595,11 +594,11 @@ class Sim:
     def render_depth(self, out, cam: np.ndarray):
         """Depth frames of every env's current state into out [N, H, W] (device, fp32);
         cam: the host camera record of mj_envs_amd.render.free_camera."""
-        n, h, w = out.shape
-        assert n == self.n_envs and out.is_contiguous(), "render_depth: out must be [n_envs, H, W]"
-        c = np.ascontiguousarray(cam, np.float32)
-        assert c.size == 17, "render_depth: camera record has 17 floats"
-        _check(load().aw_render_depth(self.h, c.ctypes.data, w, h, _ptr(out), _stream()))
+        import torch
+        _dev(out, "render_depth: out", torch.float32, (self.n_envs, None, None), optional=False)
+        _, h, w = out.shape
+        c = _record(cam, AW_CAM_FLOATS, "render_depth: camera record")
+        _check(load().aw_render_depth(self.h, _host_ptr(c), w, h, _ptr(out), _stream()))
 
     def render_rgb(self, out, cam: np.ndarray, look: Optional[np.ndarray] = None, ss: int = 1, depth=None):
         """Colour frames of every env's current state into out [N, H, W, 3] (device, uint8) and,
@@ -608,20 +607,13 @@ class Sim:
         (background rgb, headlight ambient / diffuse / specular, headlight on) or None for the
         defaults (include/adroit_wave.h aw_render_rgb)."""
         import torch
-        n, h, w, ch = out.shape
-        assert n == self.n_envs and ch == 3 and out.dtype == torch.uint8 and out.is_contiguous(), \
-            "render_rgb: out must be uint8 [n_envs, H, W, 3]"
-        if depth is not None:
-            assert tuple(depth.shape) == (n, h, w) and depth.dtype == torch.float32 and depth.is_contiguous(), \
-                "render_rgb: depth must be fp32 [n_envs, H, W]"
-        c = np.ascontiguousarray(cam, np.float32)
-        assert c.size == 17, "render_rgb: camera record has 17 floats"
-        lk = None
-        if look is not None:
-            lk = np.ascontiguousarray(look, np.float32)
-            assert lk.size == 7, "render_rgb: look record has 7 floats"
-        _check(load().aw_render_rgb(self.h, c.ctypes.data, None if lk is None else lk.ctypes.data, w, h, int(ss),
-                                    _ptr(out), _ptr(depth), _stream()))
+        _dev(out, "render_rgb: out", torch.uint8, (self.n_envs, None, None, 3), optional=False)
+        n, h, w, _ = out.shape
+        _dev(depth, "render_rgb: depth", torch.float32, (n, h, w))
+        c = _record(cam, AW_CAM_FLOATS, "render_rgb: camera record")
+        lk = _record(look, AW_LOOK_FLOATS, "render_rgb: look record")
+        _check(load().aw_render_rgb(self.h, _host_ptr(c), _host_ptr(lk), w, h, int(ss), _ptr(out), _ptr(depth),
+                                    _stream()))
 
     def render_views(self, views, width: int, height: int, rgb=None, depth=None, env_cam=None,
                      look: Optional[np.ndarray] = None, ss: int = 1):
@@ -632,29 +624,14 @@ class Sim:
         (device, fp32; ss must be 1); env_cam [N, V, 17] (device, fp32): per-env records used in
         place of the views' own; look as in render_rgb."""
         import torch
-        nv = len(views)
+        arr, nv = _views_arg(views, "render_views")
         n, w, h = self.n_envs, int(width), int(height)
-        arr = (View * max(nv, 1))()
-        for k, (rec, body) in enumerate(views):
-            c = np.ascontiguousarray(rec, np.float32)
-            assert c.size == 17, "render_views: a camera record has 17 floats"
-            arr[k].rec[:] = c.ravel().tolist()
-            arr[k].body = int(body)
-        if rgb is not None:
-            assert tuple(rgb.shape) == (n, nv, h, w, 3) and rgb.dtype == torch.uint8 and rgb.is_contiguous(), \
-                "render_views: rgb must be uint8 [n_envs, V, H, W, 3]"
-        if depth is not None:
-            assert tuple(depth.shape) == (n, nv, h, w) and depth.dtype == torch.float32 and depth.is_contiguous(), \
-                "render_views: depth must be fp32 [n_envs, V, H, W]"
-        if env_cam is not None:
-            assert tuple(env_cam.shape) == (n, nv, 17) and env_cam.dtype == torch.float32 and \
-                env_cam.is_contiguous(), "render_views: env_cam must be fp32 [n_envs, V, 17]"
-        lk = None
-        if look is not None:
-            lk = np.ascontiguousarray(look, np.float32)
-            assert lk.size == 7, "render_views: look record has 7 floats"
-        _check(load().aw_render_views(self.h, arr, nv, _ptr(env_cam), None if lk is None else lk.ctypes.data, w, h,
-                                      int(ss), _ptr(rgb), _ptr(depth), _stream()))
+        _dev(rgb, "render_views: rgb", torch.uint8, (n, nv, h, w, 3))
+        _dev(depth, "render_views: depth", torch.float32, (n, nv, h, w))
+        _dev(env_cam, "render_views: env_cam", torch.float32, (n, nv, AW_CAM_FLOATS))
+        lk = _record(look, AW_LOOK_FLOATS, "render_views: look record")
+        _check(load().aw_render_views(self.h, arr, nv, _ptr(env_cam), _host_ptr(lk), w, h, int(ss), _ptr(rgb),
+                                      _ptr(depth), _stream()))
 
     def set_appearance(self, colors=None, lights=None, look=None, shadows: bool = False):
         """Per-env appearance tables and cast shadows of the colour frames (include/adroit_wave.h
@@ -663,12 +640,10 @@ class Sim:
         handle keeps references, so they stay alive until they are replaced.  All None and
         ``shadows`` False: everything off.  Waits for the device."""
         import torch
-        ng, ns = self.render_entries()
-        for t, shape, name in ((colors, (self.n_envs, ng + ns, AW_COL_FLOATS), "colors"),
-                               (lights, (self.n_envs, self.appearance_defaults()[1].shape[0], AW_LIGHT_FLOATS), "lights"),
-                               (look, (self.n_envs, AW_LOOK_FLOATS), "look")):
-            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                                 tuple(t.shape) == shape), f"set_appearance: {name} must be device fp32 {shape}"
+        ne, nl = sum(self.render_entries()), self.appearance_defaults()[1].shape[0]
+        _dev(colors, "set_appearance: colors", torch.float32, (self.n_envs, ne, AW_COL_FLOATS))
+        _dev(lights, "set_appearance: lights", torch.float32, (self.n_envs, nl, AW_LIGHT_FLOATS))
+        _dev(look, "set_appearance: look", torch.float32, (self.n_envs, AW_LOOK_FLOATS))
         bufs = None
         if colors is not None or lights is not None or look is not None:
             bufs = AppearanceBufs(_ptr(colors), _ptr(lights), _ptr(look))
@@ -692,20 +667,17 @@ class Sim:
         given device tensors (None: not written).  env_ids: a device int32 vector, only those rows
         are written (None: every env)."""
         import torch
-        lo = np.ascontiguousarray(lo, np.float32).ravel()
-        hi = np.ascontiguousarray(hi, np.float32).ravel()
+        n = 0
+        if _dev(env_ids, "appearance_sample: env_ids", torch.int32, (None,)) is not None:
+            n = env_ids.numel() if n_sel is None else int(n_sel)
+        for k, t in (("colors", colors), ("lights", lights), ("look", look)):     # (the first dimension only)
+            _dev(t, f"appearance_sample: {k}", torch.float32,
+                 None if t is None else (self.n_envs,) + (None,) * (len(t.shape) - 1))
         ng, ns = self.render_entries()
         nf = (ng + ns) * AW_COL_FLOATS + AW_LOOK_FLOATS
         nf += AW_LIGHT_FLOATS * (lights.shape[1] if lights is not None else self.appearance_defaults()[1].shape[0])
-        assert lo.size == nf and hi.size == nf, f"appearance_sample: lo and hi hold {nf} floats"
-        n = 0
-        if env_ids is not None:
-            assert env_ids.is_cuda and env_ids.dtype == torch.int32 and env_ids.is_contiguous() and env_ids.dim() == 1, \
-                "appearance_sample: env_ids must be a device int32 vector"
-            n = env_ids.numel() if n_sel is None else int(n_sel)
-        for t in (colors, lights, look):
-            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                                 t.shape[0] == self.n_envs), "appearance_sample: outputs are device fp32 [n_envs, ...]"
+        lo = _record(lo, nf, "appearance_sample: lo")
+        hi = _record(hi, nf, "appearance_sample: hi")
         _check(load().aw_appearance_sample(self.h, lo.ctypes.data, hi.ctypes.data, _ptr(env_ids), n, int(seed), int(draw),
                                            _ptr(colors), _ptr(lights), _ptr(look), _stream()))
 
@@ -726,36 +698,20 @@ class Sim:
         of a pixel that shows nothing; sites 1: the visible sites are drawn too.  n_sel: the count
         handed to the library with env_ids (default: their number)."""
         import torch
-        nv = len(views)
+        arr, nv = _views_arg(views, "render_labels")
         w, h = int(width), int(height)
-        arr = (View * max(nv, 1))()
-        for k, (rec, body) in enumerate(views):
-            c = np.ascontiguousarray(rec, np.float32)
-            assert c.size == 17, "render_labels: a camera record has 17 floats"
-            arr[k].rec[:] = c.ravel().tolist()
-            arr[k].body = int(body)
-        n = self.n_envs
-        if env_ids is not None:
-            assert env_ids.dim() == 1 and env_ids.dtype == torch.int32 and env_ids.is_contiguous() and \
-                env_ids.is_cuda, "render_labels: env_ids must be a device int32 vector"
-            n = int(env_ids.shape[0])
-        if labels is not None:
-            assert tuple(labels.shape) == (n, nv, h, w) and labels.dtype == torch.int32 and labels.is_contiguous(), \
-                "render_labels: labels must be int32 [n, V, H, W]"
-        if depth is not None:
-            assert tuple(depth.shape) == (n, nv, h, w) and depth.dtype == torch.float32 and depth.is_contiguous(), \
-                "render_labels: depth must be fp32 [n, V, H, W]"
-        if env_cam is not None:
-            assert tuple(env_cam.shape) == (self.n_envs, nv, 17) and env_cam.dtype == torch.float32 and \
-                env_cam.is_contiguous(), "render_labels: env_cam must be fp32 [n_envs, V, 17]"
+        n = self._n_sel("render_labels", env_ids)
+        _dev(labels, "render_labels: labels", torch.int32, (n, nv, h, w))
+        _dev(depth, "render_labels: depth", torch.float32, (n, nv, h, w))
+        _dev(env_cam, "render_labels: env_cam", torch.float32, (self.n_envs, nv, AW_CAM_FLOATS))
         lt = None
         if lut is not None:
             lt = np.ascontiguousarray(lut, np.int32)
-            assert lt.ndim == 1 and lt.size == sum(self.render_entries()), \
-                "render_labels: lut has one label per render entry"
+            _require(lt.ndim == 1 and lt.size == sum(self.render_entries()),
+                     "render_labels: lut has one label per render entry")
         _check(load().aw_render_labels(self.h, arr, nv, _ptr(env_cam), _ptr(env_ids), n if n_sel is None else int(n_sel),
-                                       None if lt is None else lt.ctypes.data, int(background), int(sites), w, h,
-                                       _ptr(labels), _ptr(depth), _stream()))
+                                       _host_ptr(lt), int(background), int(sites), w, h, _ptr(labels), _ptr(depth),
+                                       _stream()))
 
     def render_cloud(self, views, width: int, height: int, xyz, count, pix=None, keep=None, box=None,
                      frame_body: int = 0, sites=0, env_cam=None, env_ids=None, cap: Optional[int] = None,
@@ -770,47 +726,29 @@ class Sim:
         are expressed in (0: the world).  cap: the capacity handed to the library (default, and the
         only one it accepts: xyz's second dimension)."""
         import torch
-        nv = len(views)
+        arr, nv = _views_arg(views, "render_cloud")
         w, h = int(width), int(height)
-        arr = (View * max(nv, 1))()
-        for k, (rec, body) in enumerate(views):
-            c = np.ascontiguousarray(rec, np.float32)
-            assert c.size == 17, "render_cloud: a camera record has 17 floats"
-            arr[k].rec[:] = c.ravel().tolist()
-            arr[k].body = int(body)
-        n = self.n_envs
-        if env_ids is not None:
-            assert env_ids.dim() == 1 and env_ids.dtype == torch.int32 and env_ids.is_contiguous() and \
-                env_ids.is_cuda, "render_cloud: env_ids must be a device int32 vector"
-            n = int(env_ids.shape[0])
-        if xyz is not None:
-            assert xyz.dim() == 3 and xyz.shape[0] == n and xyz.shape[2] == 3 and xyz.dtype == torch.float32 and \
-                xyz.is_contiguous(), "render_cloud: xyz must be fp32 [n, cap, 3]"
+        n = self._n_sel("render_cloud", env_ids)
+        if _dev(xyz, "render_cloud: xyz", torch.float32, (n, None, 3)) is not None:
             if cap is None:
                 cap = int(xyz.shape[1])
             # a cap the library refuses may be handed through; one it accepts is the row stride it writes with
-            assert cap == xyz.shape[1] or not 1 <= cap <= AW_CLOUD_MAXCAND, "render_cloud: cap is xyz's second dimension"
-        if count is not None:
-            assert tuple(count.shape) == (n,) and count.dtype == torch.int32 and count.is_contiguous(), \
-                "render_cloud: count must be int32 [n]"
+            _require(cap == xyz.shape[1] or not 1 <= cap <= AW_CLOUD_MAXCAND,
+                     "render_cloud: cap is xyz's second dimension")
+        _dev(count, "render_cloud: count", torch.int32, (n,))
         if pix is not None:
-            assert xyz is not None and tuple(pix.shape) == tuple(xyz.shape[:2]) and pix.dtype == torch.int32 and \
-                pix.is_contiguous(), "render_cloud: pix must be int32 [n, cap]"
-        if env_cam is not None:
-            assert tuple(env_cam.shape) == (self.n_envs, nv, 17) and env_cam.dtype == torch.float32 and \
-                env_cam.is_contiguous(), "render_cloud: env_cam must be fp32 [n_envs, V, 17]"
-        kp = bx = None
+            _require(xyz is not None, "render_cloud: pix needs xyz")
+            _dev(pix, "render_cloud: pix", torch.int32, tuple(xyz.shape[:2]))
+        _dev(env_cam, "render_cloud: env_cam", torch.float32, (self.n_envs, nv, AW_CAM_FLOATS))
+        kp = None
         if keep is not None:
             kp = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
-            assert kp.ndim == 1 and kp.size == sum(self.render_entries()), \
-                "render_cloud: keep has one byte per render entry"
-        if box is not None:
-            bx = np.ascontiguousarray(box, np.float32).ravel()
-            assert bx.size == 6, "render_cloud: box has 6 floats (lo xyz, hi xyz)"
+            _require(kp.ndim == 1 and kp.size == sum(self.render_entries()),
+                     "render_cloud: keep has one byte per render entry")
+        bx = _record(box, 6, "render_cloud: box (lo xyz, hi xyz)")
         _check(load().aw_render_cloud(self.h, arr, nv, _ptr(env_cam), _ptr(env_ids), n if n_sel is None else int(n_sel),
-                                      None if kp is None else kp.ctypes.data, None if bx is None else bx.ctypes.data,
-                                      int(frame_body), int(sites), w, h, 0 if cap is None else int(cap), _ptr(xyz),
-                                      _ptr(pix), _ptr(count), _stream()))
+                                      _host_ptr(kp), _host_ptr(bx), int(frame_body), int(sites), w, h,
+                                      0 if cap is None else int(cap), _ptr(xyz), _ptr(pix), _ptr(count), _stream()))
 
     def collide_test(self, types, pos, mat, size, margin, fp64: bool = False):
         """narrowphase of n primitive pairs (test hook): list of arrays [(dist, pos[3], normal[3]), ...]
@@ -838,7 +776,8 @@ class Sim:
         dev = self.torch_device
         t = lambda a, dt=torch.float32: torch.tensor(np.asarray(a), dtype=dt, device=dev).contiguous()
         args = [t(pair, torch.int32), t(pos), t(quat), t(size)]   # alive until the kernel ran
-        assert args[1].numel() == 6 * n and args[2].numel() == 8 * n and args[3].numel() == 6 * n
+        _require(args[1].numel() == 6 * n and args[2].numel() == 8 * n and args[3].numel() == 6 * n,
+                 "midphase_test: pos [n, 2, 3], quat [n, 2, 4], size [n, 2, 3]")
         info = torch.zeros(n, 6, dtype=torch.int32, device=dev)
         mg = torch.zeros(n, device=dev)
         _check(load().aw_midphase_test(self.h, n, *[_ptr(a) for a in args], _ptr(info), _ptr(mg), _stream()))
@@ -860,24 +799,14 @@ class Sim:
         arr = (DynPoint * max(len(pts), 1))()
         for k, (kind, idx) in enumerate(pts):
             arr[k].kind, arr[k].id = int(kind), int(idx)
-        n = self.n_envs
-        if env_ids is not None:
-            _ids_ok(env_ids, "dynamics: env_ids")
-            n = int(env_ids.shape[0])
-        npt = len(pts)
+        n, npt = self._n_sel("dynamics", env_ids), len(pts)
         unknown = set(out) - set(DYN_OUTPUTS)
-        assert not unknown, f"dynamics: unknown outputs {sorted(unknown)}"
+        _require(not unknown, f"dynamics: unknown outputs {sorted(unknown)}")
         c = DynOut()
         for k, t in out.items():
-            if t is None:
-                continue
-            shape = (n,) + dyn_shape(k, self.nv, self.nbody, npt)
-            assert tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda, \
-                f"dynamics: {k} must be a device fp32 {list(shape)}"
-            setattr(c, k, t.data_ptr())
-        for t, w, k in ((qpos, self.nq, "qpos"), (qvel, self.nv, "qvel"), (ctrl, self.nu, "ctrl")):
-            assert t is None or (tuple(t.shape) == (n, w) and t.dtype == torch.float32 and t.is_contiguous()
-                                 and t.is_cuda), f"dynamics: {k} must be a device fp32 [{n}, {w}]"
+            if _dev(t, f"dynamics: {k}", torch.float32, (n,) + dyn_shape(k, self.nv, self.nbody, npt)) is not None:
+                setattr(c, k, t.data_ptr())
+        self._rows("dynamics", n, qpos=qpos, qvel=qvel, ctrl=ctrl)
         _check(load().aw_dynamics(self.h, _ptr(env_ids), n if n_sel is None else int(n_sel), arr,
                                   npt if npoints is None else int(npoints), _ptr(qpos), _ptr(qvel), _ptr(ctrl),
                                   ctypes.byref(c), _stream()))
@@ -890,7 +819,7 @@ class Sim:
         rec = None if records is None else np.ascontiguousarray(records, RAY_DTYPE).ravel()
         n = (0 if rec is None else int(rec.size)) if nrays is None else int(nrays)
         # a count the library refuses may be handed through; one it accepts must lie inside the array it reads
-        assert rec is None or n <= rec.size or n > AW_MAX_RAYS, "set_rays: nrays exceeds the records given"
+        _require(rec is None or n <= rec.size or n > AW_MAX_RAYS, "set_rays: nrays exceeds the records given")
         _check(load().aw_set_rays(self.h, None if rec is None or rec.size == 0 else rec.ctypes.data, n))
         self.nrays = n
 
@@ -902,16 +831,10 @@ class Sim:
         env_rays [n_envs, R, 6] (device, fp32, indexed by env id): per-env pnt and vec in place of
         the records' own.  n_sel: the count handed to the library with env_ids."""
         import torch
-        n, R = self.n_envs, getattr(self, "nrays", 0)
-        if env_ids is not None:
-            _ids_ok(env_ids, "cast_rays: env_ids")
-            n = int(env_ids.shape[0])
-        for t, dt, what in ((dist, torch.float32, "dist"), (entry, torch.int32, "entry")):
-            assert t is None or (tuple(t.shape) == (n, R) and t.dtype == dt and t.is_contiguous() and t.is_cuda), \
-                f"cast_rays: {what} must be a device {dt} [{n}, {R}]"
-        assert env_rays is None or (tuple(env_rays.shape) == (self.n_envs, R, 6) and env_rays.dtype == torch.float32
-                                    and env_rays.is_contiguous() and env_rays.is_cuda), \
-            f"cast_rays: env_rays must be a device fp32 [{self.n_envs}, {R}, 6]"
+        n, R = self._n_sel("cast_rays", env_ids), getattr(self, "nrays", 0)
+        _dev(dist, "cast_rays: dist", torch.float32, (n, R))
+        _dev(entry, "cast_rays: entry", torch.int32, (n, R))
+        _dev(env_rays, "cast_rays: env_rays", torch.float32, (self.n_envs, R, 6))
         _check(load().aw_cast_rays(self.h, _ptr(env_ids), n if n_sel is None else int(n_sel), _ptr(env_rays),
                                    _ptr(dist), _ptr(entry), _stream()))
 

@@ -207,6 +207,22 @@ class AdroitVecEnv:
         rec, body = camera
         return np.asarray(rec, np.float32), int(body)
 
+    def _views(self, cameras, width: int, height: int):
+        """(single, views) of the ``cameras`` of ``render_segmentation`` / ``render_pointcloud``: a list of
+        ``render_views``' items, or one of them (None: the free camera), for which ``single`` is set"""
+        single = cameras is None or not isinstance(cameras, list)
+        cams = ["free" if cameras is None else cameras] if single else cameras
+        return single, [self._view(c, width, height) for c in cams]
+
+    def _upload_ids(self, env_ids, flat: bool = False):
+        """``env_ids`` given on the host as a device int32 tensor (``flat``: flattened), unchecked (the
+        library skips ids out of range); a tensor or None passes through"""
+        import torch
+        if env_ids is None or isinstance(env_ids, torch.Tensor):
+            return env_ids
+        a = np.asarray(env_ids, np.int32)
+        return torch.as_tensor(a.ravel() if flat else a, device=self.sim.torch_device)
+
     def render_views(self, cameras, width: int = 64, height: int = 64, ss: int = 1, rgb: bool = True,
                      depth: bool = False, env_cams=None, out=None, depth_out=None):
         """Several cameras of every env's current state in one launch (``aw_render_views``).
@@ -294,11 +310,9 @@ class AdroitVecEnv:
         device int32 vector or a list) between ``ranges`` = (lo, hi) of ``appearance.ranges``, into
         ``env.appearance()``'s tables, and switch them on if they are not yet (shadows stay as they
         are).  The draw of env e depends only on (seed, draw, global env id): repeatable."""
-        import torch
         lo, hi = ranges
         app = self.appearance()
-        if env_ids is not None and not isinstance(env_ids, torch.Tensor):
-            env_ids = torch.as_tensor(np.asarray(env_ids, np.int32).ravel(), device=self.sim.torch_device)
+        env_ids = self._upload_ids(env_ids, flat=True)
         if env_ids is None or env_ids.numel() > 0:
             self.sim.appearance_sample(lo, hi, app.colors, app.lights, app.look, env_ids=env_ids, seed=seed, draw=draw)
         if getattr(self, "_appearance_on", None) is not app:
@@ -320,13 +334,10 @@ class AdroitVecEnv:
         (int32, device), with ``depth`` the pair (labels, depth frames [n, V, height, width])."""
         import torch
         from .labels import label_table
-        single = cameras is None or not isinstance(cameras, list)
-        cams = ["free" if cameras is None else cameras] if single else cameras
-        views = [self._view(c, width, height) for c in cams]
+        single, views = self._views(cameras, width, height)
         if lut is None:
             lut = label_table(self.model, kind)
-        if env_ids is not None and not isinstance(env_ids, torch.Tensor):
-            env_ids = torch.as_tensor(np.asarray(env_ids, np.int32), device=self.sim.torch_device)
+        env_ids = self._upload_ids(env_ids)
         n, nv = self.num_envs if env_ids is None else int(env_ids.shape[0]), len(views)
         if out is None:
             out = self.sim.empty(n, nv, height, width, dtype=torch.int32)
@@ -364,9 +375,7 @@ class AdroitVecEnv:
         import torch
         from .labels import keep_table
         from .render import workspace_box
-        single = cameras is None or not isinstance(cameras, list)
-        cams = ["free" if cameras is None else cameras] if single else cameras
-        views = [self._view(c, width, height) for c in cams]
+        single, views = self._views(cameras, width, height)
         if isinstance(crop, str):
             if crop != "workspace":
                 raise ValueError(f"render_pointcloud: crop must be a box, 'workspace' or None, not {crop!r}")
@@ -374,8 +383,7 @@ class AdroitVecEnv:
         if isinstance(keep, (list, tuple)) and all(isinstance(k, str) for k in keep):
             keep = keep_table(self.model, keep)
         body = 0 if frame is None else (self.model.name2id("body", frame) if isinstance(frame, str) else int(frame))
-        if env_ids is not None and not isinstance(env_ids, torch.Tensor):
-            env_ids = torch.as_tensor(np.asarray(env_ids, np.int32), device=self.sim.torch_device)
+        env_ids = self._upload_ids(env_ids)
         n = self.num_envs if env_ids is None else int(env_ids.shape[0])
         cap = int(max_candidates)
         s = self.sim

@@ -17,7 +17,6 @@ through ``torch.load(weights_only=True)``): hammer / door / relocate 32x32, pen 
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Sequence
 
 import numpy as np
@@ -100,6 +99,6 @@ class GaussianMLP:
             out = torch.empty(n, self.act_dim, dtype=torch.float32, device=obs.device)
         L = _native.load()
         _native._check(L.aw_policy_mlp(n, self.obs_dim, self.hidden, self.act_dim, self._dev.data_ptr(),
-                                       obs.data_ptr(), out.data_ptr(), int(sample), ctypes.c_uint64(seed),
-                                       ctypes.c_uint64(step), ctypes.c_uint64(env_offset), _native._stream()))
+                                       obs.data_ptr(), out.data_ptr(), int(sample), seed, step, env_offset,
+                                       _native._stream()))
         return out

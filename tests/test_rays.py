@@ -5,6 +5,7 @@ is held to the checker in tests/test_gpu_rays.py."""
 import numpy as np
 import pytest
 
+import abi_header
 import ray_checker
 from conftest import load_task_model
 
@@ -215,7 +216,13 @@ def test_library_exports_rays():
     lib = _native.load()
     for s in ("aw_set_rays", "aw_cast_rays"):
         assert s in _native.EXPORTS and isinstance(getattr(lib, s), ctypes._CFuncPtr)
-    src = open(_native.os.path.join(_native.os.path.dirname(_native.HERE), "include", "adroit_wave.h")).read()
-    assert "#define AW_MAX_RAYS 256" in src and _native.AW_MAX_RAYS == 256
-    assert "float pnt[3], vec[3]; float xmax; int32_t body; uint64_t keep;" in src
+    assert abi_header.defines()["AW_MAX_RAYS"] == 256 and _native.AW_MAX_RAYS == 256
+    assert abi_header.struct_body("aw_ray_rec") == "float pnt[3], vec[3]; float xmax; int32_t body; uint64_t keep;"
+    # RAY_DTYPE is that record: the same fields in the same order, packed as the C struct is
+    ctype = {"float": "<f4", "int32_t": "<i4", "uint64_t": "<u8"}
+    want = []
+    for t, name in abi_header.struct_fields("aw_ray_rec"):
+        name, _, ext = name.partition("[")
+        want.append((name, ctype[t], (int(ext[:-1]),)) if ext else (name, ctype[t]))
+    assert _native.RAY_DTYPE == np.dtype(want) and _native.RAY_DTYPE.itemsize == 40
     assert hasattr(_native.Sim, "set_rays") and hasattr(_native.Sim, "cast_rays")

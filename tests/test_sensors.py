@@ -11,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 from conftest import ENVS, REPO, load_task_model
 import sensor_states as ss
 
@@ -19,14 +20,14 @@ NEW = ("aw_set_sensors", "aw_sensor_count", "aw_sensordata")
 
 def test_header_and_exports_list_the_sensor_calls():
     from mj_envs_amd import _native
-    src = open(os.path.join(REPO, "include", "adroit_wave.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|const char\*)\s+(aw_\w+)\s*\(", src, re.M))
+    declared = abi_header.prototypes()
     for name in NEW:
         assert name in declared, name
         assert name in _native.EXPORTS, name
         assert hasattr(_native.load(), name), name
-    # existing signatures and the dims enum are as they were
-    assert _native.AW_NDIMS == 21 and "AW_DIM_WIDE_GRID, AW_NDIMS" in src
+    # existing signatures and the dims enum are as they were: AW_NDIMS follows AW_DIM_WIDE_GRID
+    dims = abi_header.enums()
+    assert _native.AW_NDIMS == 21 and dims["AW_NDIMS"] == dims["AW_DIM_WIDE_GRID"] + 1 == 21
 
 
 @pytest.mark.parametrize("env_id", ENVS)
