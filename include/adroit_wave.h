@@ -328,6 +328,59 @@ typedef struct {
 int aw_dynamics(aw_handle* h, const int32_t* env_ids, int n_sel, const aw_dyn_point* points, int npoints,
                 const float* qpos, const float* qvel, const float* ctrl, const aw_dyn_out* out, void* stream);
 
+/* Inverse kinematics (k_ik): batched damped least squares, the whole iteration in one launch.  Given
+ * where up to AW_IK_MAXTARGETS points (and their frames) should be, find joint positions: one wave per
+ * output row runs the forward's kinematics, the residual, the Jacobian, the m x m solve and the update
+ * in LDS until the row's own residual is small, and stores the result.  No collision, no constraint
+ * solve, no posture or null-space term.  All Adroit joints are hinge or slide, so nq == nv.
+ *   env_ids / n_sel: as in aw_dynamics.  NULL: every env, n = n_envs; else a DEVICE int32 array of
+ * n = n_sel ids and output row k is env env_ids[k]; an id outside [0, n_envs) leaves row k of every
+ * output untouched; ids may repeat.
+ *   targets: a HOST array of ntargets (1..AW_IK_MAXTARGETS) records, handed to the kernel by value:
+ * kind / id as aw_dyn_point; wpos > 0 adds three position rows, wrot > 0 three orientation rows; m, the
+ * total row count, is 1..AW_IK_MAXROWS.  The orientation of a point: AW_PT_BODY and AW_PT_BODYCOM
+ * xquat[id]; AW_PT_SITE xquat[site_bodyid] * site_quat[id] (site_xmat).
+ *   goal: DEVICE [n][ntargets][7] indexed by OUTPUT ROW: position xyz, then quaternion wxyz, which the
+ * kernel normalises; a half that is not weighted is ignored; not validated.
+ *   dof_mask: bit i lets dof i move; bits at or above nv are ignored.
+ *   qpos0: NULL (the env's stored qpos is the start) or DEVICE [n][nq] indexed by output row.  The
+ * model parameters are always the env's own (body_pos, body_quat, site_pos, geom_* overrides, reset draws).
+ *   Orientation residual: the world-frame rotation vector r of d = q_goal * conj(q_cur), d negated if
+ * d.w < 0: r = 2 atan2(|d.xyz|, d.w) d.xyz / |d.xyz|, zero when |d.xyz| underflows.  It pairs with jacr.
+ *   Iteration of one row, from k = 0 while k < max_iter:
+ *     1. forward kinematics at q
+ *     2. the residual e: position rows wpos (goal - p), orientation rows wrot r
+ *     3. e non-finite: stop; |e|_2 <= tol: stop
+ *     4. J: rows wpos * jacp and wrot * jacr (aw_dynamics' definition), columns outside dof_mask zeroed
+ *     5. A = J J^T + damping I_m
+ *     6. y = A^-1 e by Cholesky (a pivot that is not > 0 -- non-finite input only -- stops the row), dq = J^T y
+ *     7. max_step > 0 and max_i |dq_i| > max_step: dq is scaled by max_step / max_i |dq_i|
+ *     8. q += dq
+ *     9. clamp_range: each masked dof with jnt_limited is clamped to jnt_range
+ *    10. k += 1
+ *   out: DEVICE buffers; err, point_pos and point_quat always belong to the returned q (after a loop
+ * that ended on max_iter the kinematics and the residual are evaluated once more):
+ *     qpos [n][nq]                 required
+ *     err [n]                      |e|_2, or NULL
+ *     iters int32 [n]              the number of updates applied, or NULL
+ *     point_pos [n][ntargets][3], point_quat [n][ntargets][4]   the targets' poses at qpos, or NULL
+ * Nothing of the simulation is written; a wave writes only its own row.  Enqueues one launch on
+ * `stream`, allocates nothing and does not wait, so it can sit inside a captured graph.
+ * AW_EINVAL (every other call still works afterwards): NULL h, targets, goal, opt, out or out->qpos;
+ * ntargets outside 1..AW_IK_MAXTARGETS; an unknown kind, an id outside its range; a negative or
+ * non-finite weight; a target with both weights 0; more than AW_IK_MAXROWS rows; dof_mask with no bit
+ * below nv; max_iter outside 0..AW_IK_MAXITER; damping not > 0 or not finite; tol < 0 or NaN; a
+ * non-finite max_step; clamp_range not 0 or 1; n_sel < 1 with env_ids. */
+#define AW_IK_MAXTARGETS 8
+#define AW_IK_MAXROWS 24
+#define AW_IK_MAXITER 64
+typedef struct { int32_t kind, id; float wpos, wrot; } aw_ik_target;
+typedef struct { int32_t max_iter; float damping, tol, max_step; int32_t clamp_range; } aw_ik_opt;
+typedef struct { float* qpos; float* err; int32_t* iters; float* point_pos; float* point_quat; } aw_ik_out;
+int aw_solve_ik(aw_handle* h, const int32_t* env_ids, int n_sel, const aw_ik_target* targets, int ntargets,
+                uint64_t dof_mask, const float* goal, const float* qpos0, const aw_ik_opt* opt, const aw_ik_out* out,
+                void* stream);
+
 /* Depth camera observation (the reference renders RGB through OpenGL:
  * headless_observer.py:20-52 -- free camera azimuth 90, distance 4.5, elevation from the
  * object / last-camera direction, 640x480 frame centre-cropped to 128x128 and resized to

@@ -115,6 +115,87 @@ class DynOut(ctypes.Structure):
     _fields_ = [(k, _vp) for k in DYN_OUTPUTS]
 
 
+# inverse kinematics (include/adroit_wave.h aw_solve_ik): the capacities and the three records
+AW_IK_MAXTARGETS, AW_IK_MAXROWS, AW_IK_MAXITER = 8, 24, 64
+IK_MAXTARGETS, IK_MAXROWS, IK_MAXITER = AW_IK_MAXTARGETS, AW_IK_MAXROWS, AW_IK_MAXITER
+IK_OUTPUTS = ("qpos", "err", "iters", "point_pos", "point_quat")
+
+
+class IKTarget(ctypes.Structure):
+    """aw_ik_target: a point of aw_solve_ik (kind AW_PT_*, body or site id) and its two weights"""
+    _fields_ = [("kind", ctypes.c_int32), ("id", ctypes.c_int32), ("wpos", ctypes.c_float), ("wrot", ctypes.c_float)]
+
+
+class IKOpt(ctypes.Structure):
+    """aw_ik_opt: the iteration's options"""
+    _fields_ = [("max_iter", ctypes.c_int32), ("damping", ctypes.c_float), ("tol", ctypes.c_float),
+                ("max_step", ctypes.c_float), ("clamp_range", ctypes.c_int32)]
+
+
+class IKOut(ctypes.Structure):
+    """aw_ik_out: the device output buffers of aw_solve_ik, NULL where not requested (qpos is required)"""
+    _fields_ = [(k, _vp) for k in IK_OUTPUTS]
+
+
+def ik_shape(name: str, nq: int, ntargets: int) -> tuple:
+    """row shape of one aw_solve_ik output"""
+    return dict(qpos=(nq,), err=(), iters=(), point_pos=(ntargets, 3), point_quat=(ntargets, 4))[name]
+
+
+def check_ik_targets(targets, nbody: int, nsite: int) -> int:
+    """aw_solve_ik's rules for the target table alone: ``targets`` a list of (kind, id, wpos, wrot);
+    returns the residual row count m.  ValueError names the rule: the target count, an unknown kind, an
+    id out of range, a negative or non-finite weight, a target with both weights 0, more than
+    ``IK_MAXROWS`` rows.  Pure: needs no GPU."""
+    tg = list(targets)
+    if not 1 <= len(tg) <= IK_MAXTARGETS:
+        raise ValueError(f"solve_ik: {len(tg)} targets, 1..{IK_MAXTARGETS} per call")
+    rows = 0
+    for kind, idx, wpos, wrot in tg:
+        if kind not in (AW_PT_BODY, AW_PT_BODYCOM, AW_PT_SITE):
+            raise ValueError(f"solve_ik: unknown target kind {kind}")
+        lim = nsite if kind == AW_PT_SITE else nbody
+        if not 0 <= int(idx) < lim:
+            raise ValueError(f"solve_ik: target id {idx} outside [0, {lim})")
+        for w in (wpos, wrot):
+            if not np.isfinite(w) or w < 0:
+                raise ValueError(f"solve_ik: a weight must be finite and >= 0, not {w}")
+        if wpos == 0 and wrot == 0:
+            raise ValueError("solve_ik: a target with both weights 0")
+        rows += (3 if wpos > 0 else 0) + (3 if wrot > 0 else 0)
+    if rows > IK_MAXROWS:
+        raise ValueError(f"solve_ik: {rows} residual rows, at most {IK_MAXROWS}")
+    return rows
+
+
+def check_ik_args(targets, dof_mask: int, nv: int, nbody: int, nsite: int, max_iter: int = 20, damping: float = 1e-4,
+                  tol: float = 1e-4, max_step: float = 0.0, clamp_range=True, n_sel=None) -> int:
+    """aw_solve_ik's argument rules on host values alone (nothing touches the GPU): the target table
+    (``check_ik_targets``), then a ``dof_mask`` with no bit below nv, ``max_iter`` outside
+    0..``IK_MAXITER``, ``damping`` not finite and > 0, ``tol`` < 0 or NaN, a non-finite ``max_step``,
+    ``clamp_range`` not 0 / 1, ``n_sel`` < 1; ValueError names the rule.  Returns the row count m."""
+    rows = check_ik_targets(targets, nbody, nsite)
+    if isinstance(dof_mask, (bool, np.bool_)) or not isinstance(dof_mask, (int, np.integer)) or \
+            not 0 <= int(dof_mask) < 1 << 64:
+        raise ValueError("solve_ik: dof_mask is an unsigned 64-bit integer")
+    if not int(dof_mask) & ((1 << nv) - 1):
+        raise ValueError(f"solve_ik: dof_mask {int(dof_mask):#x} selects no dof below nv = {nv}")
+    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)) or \
+            not 0 <= max_iter <= IK_MAXITER:
+        raise ValueError(f"solve_ik: max_iter must be an integer in 0..{IK_MAXITER}, not {max_iter}")
+    if not (np.isfinite(damping) and damping > 0):
+        raise ValueError(f"solve_ik: damping must be finite and > 0, not {damping}")
+    if not tol >= 0:
+        raise ValueError(f"solve_ik: tol must be >= 0, not {tol}")
+    if not np.isfinite(max_step):
+        raise ValueError(f"solve_ik: max_step must be finite, not {max_step}")
+    if clamp_range not in (0, 1, False, True):
+        raise ValueError(f"solve_ik: clamp_range must be 0 or 1, not {clamp_range}")
+    if n_sel is not None and n_sel < 1:
+        raise ValueError(f"solve_ik: n_sel must be >= 1, not {n_sel}")
+    return rows
+
+
 # ray queries (include/adroit_wave.h aw_set_rays / aw_cast_rays): the table's capacity and aw_ray_rec as a
 # numpy structured type (40 bytes: pnt, vec, xmax, body, keep)
 AW_MAX_RAYS = 256
@@ -159,6 +240,7 @@ ABI = {
     "aw_forward_dump": (_i, [_vp, _i, _vp, _vp, _vp]),
     "aw_forward_dump_wide": (_i, [_vp, _i, _vp, _vp, _vp]),
     "aw_dynamics": (_i, [_vp, _vp, _i, _P(DynPoint), _i, _vp, _vp, _vp, _P(DynOut), _vp]),
+    "aw_solve_ik": (_i, [_vp, _vp, _i, _P(IKTarget), _i, _u64, _vp, _vp, _P(IKOpt), _P(IKOut), _vp]),
     "aw_render_depth": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "aw_render_rgb": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "aw_render_views": (_i, [_vp, _P(View), _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -810,6 +892,37 @@ class Sim:
         _check(load().aw_dynamics(self.h, _ptr(env_ids), n if n_sel is None else int(n_sel), arr,
                                   npt if npoints is None else int(npoints), _ptr(qpos), _ptr(qvel), _ptr(ctrl),
                                   ctypes.byref(c), _stream()))
+
+    def solve_ik(self, out: dict, targets, goal, dof_mask: int, env_ids=None, qpos0=None, max_iter: int = 20,
+                 damping: float = 1e-4, tol: float = 1e-4, max_step: float = 0.0, clamp_range=True,
+                 n_sel: Optional[int] = None):
+        """Damped-least-squares inverse kinematics of the selected envs in one launch
+        (include/adroit_wave.h aw_solve_ik).  out: name -> device tensor, written in place: qpos
+        [n, nq] (required), err [n] (fp32), iters [n] (int32), point_pos [n, T, 3], point_quat [n, T, 4].
+        targets: host (kind, id, wpos, wrot) records (AW_PT_*).  goal [n, T, 7] (device, fp32): position
+        xyz and quaternion wxyz per target, by output row.  dof_mask: bit i lets dof i move.  env_ids [n]
+        (device, int32): output row k is env env_ids[k] (None: every env).  qpos0 [n, nq] (device, fp32):
+        the start, by output row (None: the env's stored qpos).  The host values are checked with
+        ``check_ik_args`` (ValueError) before anything reaches the library."""
+        import torch
+        tg = [(int(k), int(i), float(wp), float(wr)) for k, i, wp, wr in targets]
+        n = self._n_sel("solve_ik", env_ids)
+        check_ik_args(tg, dof_mask, self.nv, self.nbody, self.nsite, max_iter, damping, tol, max_step, clamp_range,
+                      n_sel if env_ids is not None else None)
+        unknown = set(out) - set(IK_OUTPUTS)
+        _require(not unknown, f"solve_ik: unknown outputs {sorted(unknown)}")
+        arr = (IKTarget * len(tg))(*[IKTarget(*t) for t in tg])
+        c = IKOut()
+        for k in IK_OUTPUTS:
+            t = _dev(out.get(k), f"solve_ik: {k}", torch.int32 if k == "iters" else torch.float32,
+                     (n,) + ik_shape(k, self.nq, len(tg)), optional=k != "qpos")
+            if t is not None:
+                setattr(c, k, t.data_ptr())
+        _dev(goal, "solve_ik: goal", torch.float32, (n, len(tg), 7), optional=False)
+        self._rows("solve_ik", n, qpos=qpos0)
+        opt = IKOpt(int(max_iter), float(damping), float(tol), float(max_step), int(clamp_range))
+        _check(load().aw_solve_ik(self.h, _ptr(env_ids), n if n_sel is None else int(n_sel), arr, len(tg),
+                                  int(dof_mask), _ptr(goal), _ptr(qpos0), ctypes.byref(opt), ctypes.byref(c), _stream()))
 
     def set_rays(self, records, nrays: Optional[int] = None):
         """Upload the handle's ray table (include/adroit_wave.h aw_set_rays): ``records`` a host array

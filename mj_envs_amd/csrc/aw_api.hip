@@ -845,6 +845,46 @@ int aw_dynamics(aw_handle* h, const int32_t* env_ids, int n_sel, const aw_dyn_po
   return AW_OK;
 }
 
+int aw_solve_ik(aw_handle* h, const int32_t* env_ids, int n_sel, const aw_ik_target* targets, int ntargets,
+                uint64_t dof_mask, const float* goal, const float* qpos0, const aw_ik_opt* opt, const aw_ik_out* out,
+                void* stream) {
+  if (!h || !targets || !goal || !opt || !out || !out->qpos)
+    return fail(AW_EINVAL, "aw_solve_ik: null handle, targets, goal, opt, out or out->qpos");
+  if (ntargets < 1 || ntargets > AW_IK_MAXTARGETS) return fail(AW_EINVAL, "aw_solve_ik: ntargets must be 1..AW_IK_MAXTARGETS");
+  if (env_ids && n_sel < 1) return fail(AW_EINVAL, "aw_solve_ik: n_sel must be >= 1 with env_ids");
+  IkTgt tg = {};   // a kernel argument, as the points of aw_dynamics are
+  int rows = 0;
+  for (int p = 0; p < ntargets; p++) {
+    const aw_ik_target& t = targets[p];
+    if (t.kind != AW_PT_BODY && t.kind != AW_PT_BODYCOM && t.kind != AW_PT_SITE)
+      return fail(AW_EINVAL, "aw_solve_ik: a target's kind is none of AW_PT_BODY, AW_PT_BODYCOM, AW_PT_SITE");
+    if (t.id < 0 || t.id >= (t.kind == AW_PT_SITE ? h->m.nsite : h->m.nbody))
+      return fail(AW_EINVAL, "aw_solve_ik: a target's id is not a body / site of the model");
+    if (!std::isfinite(t.wpos) || !std::isfinite(t.wrot) || t.wpos < 0.f || t.wrot < 0.f)
+      return fail(AW_EINVAL, "aw_solve_ik: a target's weights must be finite and >= 0");
+    if (t.wpos == 0.f && t.wrot == 0.f) return fail(AW_EINVAL, "aw_solve_ik: a target with both weights 0");
+    tg.kind[p] = t.kind;
+    tg.id[p] = t.id;
+    tg.row[p] = rows;
+    tg.wpos[p] = t.wpos;
+    tg.wrot[p] = t.wrot;
+    rows += (t.wpos > 0.f ? 3 : 0) + (t.wrot > 0.f ? 3 : 0);
+  }
+  if (rows > AW_IK_MAXROWS) return fail(AW_EINVAL, "aw_solve_ik: more than AW_IK_MAXROWS residual rows");
+  const uint64_t below_nv = h->m.nv < 64 ? (1ull << h->m.nv) - 1ull : ~0ull;
+  if (!(dof_mask & below_nv)) return fail(AW_EINVAL, "aw_solve_ik: dof_mask selects no dof of the model");
+  if (opt->max_iter < 0 || opt->max_iter > AW_IK_MAXITER) return fail(AW_EINVAL, "aw_solve_ik: max_iter must be 0..AW_IK_MAXITER");
+  if (!(opt->damping > 0.f) || !std::isfinite(opt->damping)) return fail(AW_EINVAL, "aw_solve_ik: damping must be finite and > 0");
+  if (!(opt->tol >= 0.f)) return fail(AW_EINVAL, "aw_solve_ik: tol must be >= 0");
+  if (!std::isfinite(opt->max_step)) return fail(AW_EINVAL, "aw_solve_ik: max_step must be finite");
+  if (opt->clamp_range != 0 && opt->clamp_range != 1) return fail(AW_EINVAL, "aw_solve_ik: clamp_range must be 0 or 1");
+  HIPCHK(hipSetDevice(h->device));
+  h->ops->ik(h, env_ids, env_ids ? n_sel : h->nenv, tg, ntargets, rows, dof_mask & below_nv, goal, qpos0, *opt, *out,
+             (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return AW_OK;
+}
+
 static_assert(sizeof(aw_ray_rec) == 40 && offsetof(aw_ray_rec, keep) == 32, "aw_ray_rec is 40 bytes");
 int aw_set_rays(aw_handle* h, const aw_ray_rec* rays, int nrays) {
   if (!h) return fail(AW_EINVAL, "aw_set_rays: null");

@@ -53,6 +53,12 @@ struct CloudRec {
 struct DynPts {
   int kind[AW_DYN_MAXPOINTS], id[AW_DYN_MAXPOINTS];
 };
+// the target table of one aw_solve_ik launch (k_ik, aw_ik.h): kind (AW_PT_*), object id, the two weights
+// and the first residual row of each target
+struct IkTgt {
+  int kind[AW_IK_MAXTARGETS], id[AW_IK_MAXTARGETS], row[AW_IK_MAXTARGETS];
+  float wpos[AW_IK_MAXTARGETS], wrot[AW_IK_MAXTARGETS];
+};
 // the per-env appearance tables of aw_set_appearance (k_views_app): the caller's device buffers,
 // [N][ne][COL_W], [N][nlight][LIGHT_W], [N][AW_LOOK_FLOATS]; nullptr: the model's / the launch's look
 struct AppRec {
@@ -165,6 +171,8 @@ struct TaskOps {
   void (*dyn)(aw_handle*, const int32_t*, int, const DynPts&, int, const float*, const float*, const float*,
               const aw_dyn_out&, hipStream_t);
   void (*rays)(aw_handle*, const int32_t*, int, const float*, float*, int32_t*, hipStream_t);
+  void (*ik)(aw_handle*, const int32_t*, int, const IkTgt&, int, int, uint64_t, const float*, const float*,
+             const aw_ik_opt&, const aw_ik_out&, hipStream_t);
 };
 template <int TASK> const TaskOps* task_ops();
 

@@ -1,7 +1,7 @@
 // aw_kernels.hip -- the kernels of ONE task and the launcher table that hands them to the API unit
 // (aw_api.hip).  The library holds this file eight times (__graft_entry__.py): per task once with
 // -DAW_TASK_TU=<task> (the fast tier: k_step, k_reset, k_set_state, k_set_state_ids, k_dump, k_depth, k_rgb, k_views,
-// k_views_app, k_labels, k_cloud, k_dyn (aw_dyn.h), k_rays (aw_rays.h), k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide
+// k_views_app, k_labels, k_cloud, k_dyn (aw_dyn.h), k_rays (aw_rays.h), k_ik (aw_ik.h), k_order and task_ops<task>) and once with -DAW_TASK_TU=<task> -DAW_WIDE (the wide
 // tier: k_step_wide, k_dump_wide and wide_ops<task>).  AW_WIDE is the tier switch of aw_common.h's capacities; the
 // env-step both tiers run is aw_step.h.  Written once: finish_forward (the tail of k_reset and the set-state kernels),
 // set_state_body (both set-state kernels), stage_pose / view_cam (the render kernels' prologue and per-view camera).
@@ -20,6 +20,7 @@
 #ifndef AW_WIDE
 #include "aw_dyn.h"   // k_dyn: the fast-tier unit only
 #include "aw_rays.h"  // k_rays: likewise
+#include "aw_ik.h"    // k_ik: likewise
 #endif
 
 using namespace aw;
@@ -830,11 +831,19 @@ static void launch_rays(aw_handle* h, const int32_t* env_ids, int grid, const fl
   hipLaunchKernelGGL((k_rays<TASK>), dim3(grid), dim3(64 * ((h->nrays + 63) / 64)), 0, st, h->m, h->st, h->nenv, env_ids,
                      (const RayRec*)h->rays, h->nrays, env_rays, dist, entry);
 }
+// grid: the output rows (the selected envs, or all of them)
+template <int TASK>
+static void launch_ik(aw_handle* h, const int32_t* env_ids, int grid, const IkTgt& tg, int ntargets, int mrows,
+                      uint64_t dof_mask, const float* goal, const float* qpos0, const aw_ik_opt& opt, const aw_ik_out& out,
+                      hipStream_t st) {
+  hipLaunchKernelGGL((k_ik<TASK>), dim3(grid), dim3(64), 0, st, h->m, h->st, h->nenv, env_ids, tg, ntargets, mrows,
+                     (unsigned long long)dof_mask, goal, qpos0, opt, out);
+}
 template <int TASK> const TaskOps* task_ops() {
   static const TaskOps ops = {[](int device) { return resident_slots(k_step<TASK, false, false>, device); },  // the persistent grid
                               launch_step<TASK>, launch_reset<TASK>, launch_set<TASK>, launch_set_ids<TASK>,
                               launch_dump<TASK>, launch_depth<TASK>, launch_rgb<TASK>, launch_views<TASK>,
-                              launch_labels<TASK>, launch_cloud<TASK>, launch_dyn<TASK>, launch_rays<TASK>};
+                              launch_labels<TASK>, launch_cloud<TASK>, launch_dyn<TASK>, launch_rays<TASK>, launch_ik<TASK>};
   return &ops;
 }
 template const TaskOps* task_ops<AW_TASK_TU>();

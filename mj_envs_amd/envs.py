@@ -554,6 +554,20 @@ class AdroitVecEnv:
         from .dynamics import evaluate
         return evaluate(self, points, env_ids, want, qpos, qvel, actions, ctrl, out)
 
+    # --- inverse kinematics (mj_envs_amd/ik.py) --------------------------------------------------
+    def solve_ik(self, targets, goal_pos=None, goal_quat=None, dofs=None, env_ids=None, qpos0=None, out=None,
+                 **opt):
+        """Joint positions that put the ``targets`` (an ``ik.targets(...)`` table) at ``goal_pos``
+        [n, T, 3] / ``goal_quat`` [n, T, 4] (wxyz; device, one row per output row) for every env, or
+        for ``env_ids`` (a list, a numpy array or a device int32 tensor; ids may repeat): damped least
+        squares, the whole iteration in one launch (``aw_solve_ik``).  ``dofs``: an ``ik.dof_mask(...)``
+        mask of the dofs that may move (None: every actuated dof).  ``qpos0`` [n, nq]: the start (None:
+        the env's own qpos).  Options: ``max_iter`` 20, ``damping`` 1e-4, ``tol`` 1e-4, ``max_step`` 0
+        (no limit), ``clamp_range`` True.  ``out``: an earlier result whose buffers are reused where
+        the shapes agree.  The simulation is not touched.  Returns an ``ik.IKResult``."""
+        from .ik import solve
+        return solve(self, targets, goal_pos, goal_quat, dofs, env_ids, qpos0, out, opt)
+
     def get_episode(self):
         """the running episode of every env: ep_len, ep_ret, ep_goal, and the finished-episode count"""
         import torch
@@ -699,6 +713,17 @@ class _AdroitEnv(_reference_base()):
             ctrl = torch.as_tensor(self.vec.act_mid, device=self._dev) + a * torch.as_tensor(self.vec.act_rng,
                                                                                                device=self._dev)
         return EnvDynamics(self.vec, ctrl)
+
+    def solve_ik(self, targets, goal_pos=None, goal_quat=None, dofs=None, qpos0=None, **opt):
+        """``AdroitVecEnv.solve_ik`` for this env with numpy in and out: ``goal_pos`` [T, 3],
+        ``goal_quat`` [T, 4], ``qpos0`` [nq] -> dict of float64 numpy ``qpos`` [nq], ``err``, ``iters``,
+        ``converged``, ``point_pos`` [T, 3], ``point_quat`` [T, 4].  The simulation is not touched."""
+        import torch
+        up = lambda a: None if a is None else torch.as_tensor(np.asarray(a, np.float32), device=self._dev)[None]
+        r = self.vec.solve_ik(targets, up(goal_pos), up(goal_quat), dofs=dofs, qpos0=up(qpos0), **opt)
+        f = lambda t: t[0].cpu().numpy().astype(np.float64)
+        return dict(qpos=f(r.qpos), err=float(r.err[0]), iters=int(r.iters[0]), converged=bool(r.converged[0]),
+                    point_pos=f(r.point_pos), point_quat=f(r.point_quat))
 
     def ray(self, pnt, vec, geomgroup=None, flg_static=1, bodyexclude=-1):
         """``mj_ray(m, d, pnt, vec, geomgroup, flg_static, bodyexclude, geomid)`` at the current state:
