@@ -448,7 +448,7 @@ int aw_create(const void* blob, size_t nbytes, int n_envs, int device, aw_handle
   if (int rc = build_model(B, h->m, *md, sens, data, err)) return fail(rc, err);
   h->NV = h->m.nv;
   h->nsensor = sens.n;
-  if (int rc = check_tree(B, h->m.task_kind, err)) return fail(rc, err);
+  if (int rc = check_tree(B, h->m.task_kind, *md, err)) return fail(rc, err);
   std::vector<float> def;   // default params of every env
   if (int rc = param_defaults(B, h->m.nparam, def, err)) return fail(rc, err);
   h->ops = task_ops_of(h->m.task_kind);

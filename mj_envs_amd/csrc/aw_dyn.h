@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(64) k_dyn(DModel m, DState st, int n, const in
 
   if (o.qM || o.qMinv) {
     float Mrow[NV];
-    stage_crb<NV>(m, s, lane, Mrow);
+    stage_crb<TASK>(m, s, lane, Mrow);
     const size_t base = row * NV * NV + lane;
     if (o.qM && lane < NV)
 #pragma unroll

@@ -7,6 +7,7 @@
 #pragma once
 #include "aw_common.h"
 #include "aw_sincos64.h"
+#include "aw_tree.h"
 
 namespace aw {
 
@@ -54,17 +55,27 @@ AW_DEV void apply_ovr(const DModel& m, const Env& s, int field, int obj, float (
 #ifndef AW_JNT_REC
 #define AW_JNT_REC 1
 #endif
+// AW_SITES_LAST (default 1; 0 restores the earlier text): stage_kinematics builds sxpos / txmat only
+// when `sites` is set.  They are read by the task layer, stage_touch, stage_sensors, stage_data and
+// the kernels outside the env-step -- inside an env-step only after the last substep's forward, so
+// forward() passes the flag it already has for stage_touch.  No arithmetic operation, operand or
+// order changes.
+#ifndef AW_SITES_LAST
+#define AW_SITES_LAST 1
+#endif
+
 constexpr int JREC_W = 12;   // {axis, hinge} {anchor, q} {joint quaternion}
 static_assert(MAXV * JREC_W <= JL * VS && (JREC_W * 4) % 16 == 0, "fp32 joint records do not fit in the dense-J rows");
 AW_DEV MRec* jnt_rec32(Env& s, int j) { return reinterpret_cast<MRec*>(&s.J[0][0]) + (JREC_W / 4) * j; }
 
 // mj_kinematics (+ local2global for geoms, sites).  Frames are kept as quaternions only: every
 // position update rotates by the (normalised) quaternion instead of a stored rotation matrix.
-AW_DEV void stage_kinematics(const DModel& m, Env& s, int lane) {
+AW_DEV void stage_kinematics(const DModel& m, Env& s, int lane, bool sites = true) {
   if (lane == 0) {
     s.xpos[0][0] = s.xpos[0][1] = s.xpos[0][2] = 0;
     s.xquat[0][0] = 1; s.xquat[0][1] = s.xquat[0][2] = s.xquat[0][3] = 0;
   }
+  const bool do_sites = !AW_SITES_LAST || sites;
 #if AW_JNT_REC
   if (lane < m.njnt) {
     const int j = lane;
@@ -194,7 +205,7 @@ AW_DEV void stage_kinematics(const DModel& m, Env& s, int lane) {
     mulq(q, bq, gq);
     for (int c = 0; c < 4; c++) s.gxquat[g][c] = q[c];
   }
-  for (int i = lane; i < m.nsite; i += 64) {
+  for (int i = lane; do_sites && i < m.nsite; i += 64) {
     int b = MD(site_bodyid, i);
     float v[3], sp[3], bq[4];
     for (int c = 0; c < 3; c++) sp[c] = MD(site_pos, 3 * i + c);
@@ -203,7 +214,7 @@ AW_DEV void stage_kinematics(const DModel& m, Env& s, int lane) {
     rotvq(v, sp, bq);
     add3(s.sxpos[i], v, s.xpos[b]);
   }
-  if (lane < m.ntouch) {
+  if (do_sites && lane < m.ntouch) {
     int i = MD(touch_site, lane), b = MD(site_bodyid, i);
     float q[4], sq[4];
     for (int c = 0; c < 4; c++) sq[c] = MD(site_quat, 4 * i + c);
@@ -411,8 +422,22 @@ AW_DEV void stage_com(const DModel& m, Env& s, int lane) {
 // mj_crb -> M row per lane (registers).  Runs after RNE: the composite inertias overwrite
 // cinert in place.  M[i][k] = cdof_k . (crb_{body i} cdof_i) for k an ancestor of i, symmetric
 // for descendants, + armature on the diagonal.
-template <int NV>
-AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[NV]) {
+// AW_CRB_TREE (default 1): which entries of the row are structural comes from the task's compiled dof
+// tree (aw_tree.h: one constant dof mask per column, tested against this lane's dof bit) instead of
+// the model table's dof_ancmask (a uniform load and two 64-bit shifts per column, every substep).
+// aw_create refuses a model whose table disagrees with the compiled tree (aw_model_host.h check_tree).
+#ifndef AW_CRB_TREE
+#define AW_CRB_TREE 1
+#endif
+template <int TASK, int... K>
+AW_DEV void crb_row_tree(float (&Mrow)[Tree<TASK>::NV], const float (&row)[Tree<TASK>::NV], int li, float arm,
+                         std::integer_sequence<int, K...>) {
+  const unsigned long long me = 1ull << li;   // li < NV: a lane past the dofs stands for dof NV - 1
+  ((Mrow[K] = K == li ? row[K] + arm : ((TRelMask<TASK, K>::v & me) != 0ull ? row[K] : 0.f)), ...);
+}
+template <int TASK>
+AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>::NV]) {
+  constexpr int NV = Tree<TASK>::NV;
   float acc[10];
   for (int k = 0; k < 10; k++) acc[k] = 0;
   const int bb = lane < m.nbody ? lane : 0;
@@ -430,7 +455,9 @@ AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[NV]) {
   mul_inert_vec(bi, s.cinert[MD(dof_bodyid, li)], ci);
   for (int k = 0; k < 6; k++) s.buf[li][k] = bi[k];
   wsync();
+#if !AW_CRB_TREE
   const unsigned long long anc = MD(dof_ancmask, li);
+#endif
   const float arm = MD(dof_armature, li);
   // P = B C' on the matrix cores (B: rows b_i = crb_{body i} cdof_i, C: rows cdof_k; K = 6 padded
   // to two K-steps of v_mfma_f32_16x16x4_f32), lower tiles only.  M[i][k] = P[i][k] for k an
@@ -486,6 +513,20 @@ AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[NV]) {
         }
     wsync();
     const float* Sr = S + li * SS;
+#if AW_CRB_TREE
+    {
+      float row[NV];
+#pragma unroll
+      for (int q = 0; q < (NV + 3) / 4; q++) {
+        const float4 v4 = *reinterpret_cast<const float4*>(Sr + 4 * q);
+        const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+          if (4 * q + t < NV) row[4 * q + t] = vv[t];
+      }
+      crb_row_tree<TASK>(Mrow, row, li, arm, std::make_integer_sequence<int, NV>{});
+    }
+#else
 #pragma unroll
     for (int q = 0; q < (NV + 3) / 4; q++) {
       const float4 v4 = *reinterpret_cast<const float4*>(Sr + 4 * q);
@@ -498,22 +539,9 @@ AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[NV]) {
         Mrow[k] = k == li ? vv[t] + arm : (rel ? vv[t] : 0.f);
       }
     }
+#endif
     wsync();
-    return;
   }
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-    float ck[6], bk[6];
-    for (int c = 0; c < 6; c++) { ck[c] = s.cdof[k][c]; bk[c] = s.buf[k][c]; }
-    const unsigned long long anck = MD(dof_ancmask, k);
-    float v;
-    if (k == li) v = dot6(ci, bi) + arm;
-    else if ((anc >> k) & 1ull) v = dot6(ck, bi);
-    else if ((anck >> li) & 1ull) v = dot6(ci, bk);
-    else v = 0.f;
-    Mrow[k] = v;
-  }
-  wsync();
 }
 
 // mj_fwdActuation's scalar force of actuator u (joint transmission on dof j, gear `gear`): gain *

@@ -679,4 +679,34 @@ inline int check_tree(const Blob& B, int task_kind, std::string& err) {
   return AW_OK;
 }
 
+// ... and so must the built table's ancestor masks: stage_crb takes the structure of M from the
+// compiled tree (AW_CRB_TREE) while the solver stages read dof_ancmask, and the two must describe
+// one tree.  The masks are compared bit for bit, rows past nv included (they must be empty).
+template <int TASK>
+bool ancmask_matches(const MData& md) {
+  for (int j = 0; j < MAXV; j++) {
+    unsigned long long want = 0;
+    if (j < TreeDef<TASK>::NV)
+      for (int p = TreeDef<TASK>::parent[j]; p >= 0; p = TreeDef<TASK>::parent[p]) want |= 1ull << p;
+    if (md.dof_ancmask[j] != want) return false;
+  }
+  return true;
+}
+inline int check_tree(const Blob& B, int task_kind, const MData& md, std::string& err) {
+  if (int rc = check_tree(B, task_kind, err)) return rc;
+  bool ok = false;
+  switch (task_kind) {
+    case 0: ok = ancmask_matches<0>(md); break;
+    case 1: ok = ancmask_matches<1>(md); break;
+    case 2: ok = ancmask_matches<2>(md); break;
+    case 3: ok = ancmask_matches<3>(md); break;
+  }
+  if (!ok) {
+    err = "model table's dof_ancmask differs from the compiled dof tree of its task "
+          "(mj_envs_amd/csrc/aw_trees.h: run tools/gen_trees.py and rebuild)";
+    return AW_EUNSUPPORTED;
+  }
+  return AW_OK;
+}
+
 }  // namespace aw

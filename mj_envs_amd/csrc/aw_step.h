@@ -277,7 +277,7 @@ template <int TASK, bool ROWST = false>
 AW_DEV void forward(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>::NV], Dof& d, float* rowst = nullptr,
                     bool touch = true) {
   constexpr int NV = Tree<TASK>::NV;
-  stage_kinematics(m, s, lane);
+  stage_kinematics(m, s, lane, touch);   // AW_SITES_LAST: sxpos / txmat have the readers s.touch has
   AW_PROF(s, PR_KIN);
   stage_collision(m, s, lane);
   AW_PROF(s, PR_COLL);
@@ -285,7 +285,7 @@ AW_DEV void forward(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK>:
   AW_PROF(s, PR_COM);
   d.qfrc_smooth = stage_velocity(m, s, lane);
   AW_PROF(s, PR_RNE);
-  stage_crb<NV>(m, s, lane, Mrow);
+  stage_crb<TASK>(m, s, lane, Mrow);
   AW_PROF(s, PR_CRB);
   if (lane == 0) { s.it_newton = 1000 * NT_EXIT_NOROWS; s.it_noslip = 0; }
   stage_constraints<NV>(m, s, lane);

@@ -56,6 +56,20 @@ template <int TASK> struct Tree {
     return 0;
   }
   static constexpr int SPLIT = split();
+  // the strict ancestors of dof j as a bit mask over dofs (the model table's dof_ancmask[j])
+  static constexpr unsigned long long ancmask(int j) {
+    unsigned long long a = 0;
+    for (int p = D::parent[j]; p >= 0; p = D::parent[p]) a |= 1ull << p;
+    return a;
+  }
+  // the dofs whose row of M has a structural off-diagonal entry in column k: the strict ancestors
+  // and the descendants of k, as a bit mask over dofs
+  static constexpr unsigned long long relmask(int k) {
+    unsigned long long r = ancmask(k);
+    for (int i = 0; i < NV; i++)
+      if ((ancmask(i) >> k) & 1ull) r |= 1ull << i;
+    return r;
+  }
   static constexpr bool ordered() {   // ancestors before descendants (MuJoCo's dof order)
     for (int j = 0; j < NV; j++)
       if (D::parent[j] >= j) return false;
@@ -65,6 +79,7 @@ template <int TASK> struct Tree {
 // constants forced at compile time (template arguments of every register index below)
 template <int TASK, int J> struct TDepth { static constexpr int v = Tree<TASK>::depth(J); };
 template <int TASK, int J, int A> struct TAnc { static constexpr int v = Tree<TASK>::anc(J, A); };
+template <int TASK, int K> struct TRelMask { static constexpr unsigned long long v = Tree<TASK>::relmask(K); };
 
 namespace tree {
 template <int TASK> using Row = float[Tree<TASK>::NV];
