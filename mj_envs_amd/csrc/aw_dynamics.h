@@ -63,6 +63,15 @@ AW_DEV void apply_ovr(const DModel& m, const Env& s, int field, int obj, float (
 #ifndef AW_SITES_LAST
 #define AW_SITES_LAST 1
 #endif
+// AW_TAIL_HEADS (default 1; 0 restores the earlier text): the model reads at the end of three stages
+// are issued ahead of the LDS phase before them, at clamped indices, and selected afterwards --
+// stage_velocity's dof_bodyid / dof_damping / dof_act at its top and the actuator's eleven act_* reads
+// before the subtree sums, stage_crb's dof_bodyid / dof_armature before its subtree sums, and the
+// near-margin pass of stage_collision (aw_step.h) reads cp_pack / cp_margin / cp_kin64 of a contact
+// lane's pair as one clause.  Same loads and arithmetic; only where the loads are issued changes.
+#ifndef AW_TAIL_HEADS
+#define AW_TAIL_HEADS 1
+#endif
 
 constexpr int JREC_W = 12;   // {axis, hinge} {anchor, q} {joint quaternion}
 static_assert(MAXV * JREC_W <= JL * VS && (JREC_W * 4) % 16 == 0, "fp32 joint records do not fit in the dense-J rows");
@@ -441,6 +450,11 @@ AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK
   float acc[10];
   for (int k = 0; k < 10; k++) acc[k] = 0;
   const int bb = lane < m.nbody ? lane : 0;
+  const int li = lane < NV ? lane : NV - 1;
+#if AW_TAIL_HEADS
+  const int dbid = MD(dof_bodyid, li);
+  const float arm = MD(dof_armature, li);
+#endif
   if (lane < m.nbody && lane > 0)
 #pragma unroll AW_SUB_UNROLL
     for (int d = bb; d < MD(body_subtree_end, bb); d++)
@@ -449,16 +463,21 @@ AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK
   if (lane < m.nbody)
     for (int k = 0; k < 10; k++) s.cinert[bb][k] = acc[k];
   wsync();
-  const int li = lane < NV ? lane : NV - 1;
   float ci[6], bi[6];
   for (int k = 0; k < 6; k++) ci[k] = s.cdof[li][k];
+#if AW_TAIL_HEADS
+  mul_inert_vec(bi, s.cinert[dbid], ci);
+#else
   mul_inert_vec(bi, s.cinert[MD(dof_bodyid, li)], ci);
+#endif
   for (int k = 0; k < 6; k++) s.buf[li][k] = bi[k];
   wsync();
 #if !AW_CRB_TREE
   const unsigned long long anc = MD(dof_ancmask, li);
 #endif
+#if !AW_TAIL_HEADS
   const float arm = MD(dof_armature, li);
+#endif
   // P = B C' on the matrix cores (B: rows b_i = crb_{body i} cdof_i, C: rows cdof_k; K = 6 padded
   // to two K-steps of v_mfma_f32_16x16x4_f32), lower tiles only.  M[i][k] = P[i][k] for k an
   // ancestor of i and P[k][i] for a descendant, so each lower entry is stored at (i, k) and
@@ -470,6 +489,8 @@ AW_DEV void stage_crb(const DModel& m, Env& s, int lane, float (&Mrow)[Tree<TASK
     constexpr int NT = (NV + 15) / 16, SS = VS;
     static_assert(offsetof(Env, rowbuf) == offsetof(Env, J) + sizeof(float) * JL * VS &&
                   MAXV * SS <= JL * VS + MAXEFC, "CRB staging block does not fit the dense-J rows + rowbuf");
+    // lane li reads its staging row back through float4 casts: the block and every row start on 16 bytes
+    static_assert(offsetof(Env, J) % 16 == 0 && (SS * sizeof(float)) % 16 == 0, "CRB staging rows are read as float4");
     float* S = &s.J[0][0];
     const int sub = lane >> 4, col = lane & 15;
     f4 acc[NT][NT];
@@ -564,6 +585,12 @@ AW_DEV float actuator_force(const DModel& m, const Env& s, int u, int j, float g
 AW_DEV float stage_velocity(const DModel& m, Env& s, int lane) {
   float (*cvel)[6] = s.cvel;
   float (*cacc)[6] = s.cacc;
+#if AW_TAIL_HEADS
+  // the tail's per-dof reads, issued ahead of the tree sums (dof 0 for the lanes past the dofs)
+  const int tj = lane < m.nv ? lane : 0;
+  const int t_bid = MD(dof_bodyid, tj), t_act = MD(dof_act, tj);
+  const float t_damp = MD(dof_damping, tj);
+#endif
   if (lane == 0) {
     for (int k = 0; k < 6; k++) { cvel[0][k] = 0; cacc[0][k] = 0; }
     if (!(m.disableflags & DSBL_GRAVITY)) { cacc[0][3] = -m.gravity[0]; cacc[0][4] = -m.gravity[1]; cacc[0][5] = -m.gravity[2]; }
@@ -637,6 +664,15 @@ AW_DEV float stage_velocity(const DModel& m, Env& s, int lane) {
   float sub[6];
   const int bb = lane < m.nbody ? lane : 0;
   for (int k = 0; k < 6; k++) sub[k] = 0;
+#if AW_TAIL_HEADS
+  // the driving actuator's parameters (actuator 0 for a dof without one: never used)
+  const int tu = t_act >= 0 ? t_act : 0;
+  const int t_cl = MD(act_ctrllimited, tu), t_fl = MD(act_forcelimited, tu);
+  const float t_cr0 = MD(act_ctrlrange, 2 * tu), t_cr1 = MD(act_ctrlrange, 2 * tu + 1);
+  const float t_gear = MD(act_gear, tu), t_gain = MD(act_gain, tu);
+  const float t_b0 = MD(act_bias, 3 * tu), t_b1 = MD(act_bias, 3 * tu + 1), t_b2 = MD(act_bias, 3 * tu + 2);
+  const float t_fr0 = MD(act_forcerange, 2 * tu), t_fr1 = MD(act_forcerange, 2 * tu + 1);
+#endif
   if (lane < m.nbody && lane > 0)
 #pragma unroll AW_SUB_UNROLL
     for (int d = bb; d < MD(body_subtree_end, bb); d++)
@@ -646,6 +682,25 @@ AW_DEV float stage_velocity(const DModel& m, Env& s, int lane) {
     for (int k = 0; k < 6; k++) cvel[bb][k] = sub[k];
   wsync();
   float qfrc = 0.f;
+#if AW_TAIL_HEADS
+  if (lane < m.nv) {
+    int j = lane;
+    float bias = dot6(s.cdof[j], cvel[t_bid]);
+    float pas = (m.disableflags & DSBL_PASSIVE) ? 0.f : -t_damp * s.qvel[j];
+    float act = 0.f;
+    int u = t_act;
+    if (u >= 0 && !(m.disableflags & DSBL_ACTUATION)) {
+      float ctrl = s.ctrl[u];
+      if (t_cl && !(m.disableflags & DSBL_CLAMPCTRL)) ctrl = clampf(ctrl, t_cr0, t_cr1);
+      float gear = t_gear;
+      float len = gear * s.qpos[j], vel = gear * s.qvel[j];
+      float f = t_gain * ctrl + t_b0 + t_b1 * len + t_b2 * vel;
+      if (t_fl) f = clampf(f, t_fr0, t_fr1);
+      act = gear * f;
+    }
+    qfrc = pas - bias + act;
+  }
+#else
   if (lane < m.nv) {
     int j = lane;
     float bias = dot6(s.cdof[j], cvel[MD(dof_bodyid, j)]);
@@ -665,6 +720,7 @@ AW_DEV float stage_velocity(const DModel& m, Env& s, int lane) {
     }
     qfrc = pas - bias + act;
   }
+#endif
   wsync();
   return qfrc;
 }

@@ -279,6 +279,16 @@ AW_DEV float jt_mul(const DModel& m, Env& s, int lane, float* absum = nullptr) {
 
 // ---------------------------------------------------------------------------------------
 // mj_makeConstraint + mj_makeImpedance + reference acceleration
+// AW_CS_HEAD (default 1; 0 restores the earlier text): the model reads of the frictionloss, joint-limit
+// and tendon-limit arms and of the contact rows are issued together at the top of the stage, at clamped
+// indices, and the arms select from the loaded values.  Before, each arm loaded inside its own lane
+// condition (fl_dof -> dof_frictionloss, jnt_limited -> jnt_range64, ten_limited -> ten_d0 ->
+// ten_c0_64, con_pair -> cp_condim -> cp_tran ...), one load latency after another on the wave's serial
+// path, and the dense-row chunk loaded cp_mask / cp_root / cp_friction of the same pair again.
+// Same loads, same values, same arithmetic; only where the loads are issued changes.
+#ifndef AW_CS_HEAD
+#define AW_CS_HEAD 1
+#endif
 template <int NV>
 AW_DEV void stage_constraints(const DModel& m, Env& s, int lane) {
   if (m.disableflags & DSBL_CONSTRAINT) {
@@ -287,6 +297,110 @@ AW_DEV void stage_constraints(const DModel& m, Env& s, int lane) {
     return;
   }
   const int nfl = (m.disableflags & DSBL_FRICTIONLOSS) ? 0 : m.nfl;
+#if AW_CS_HEAD
+  // Load head.  Every model read of the three sparse arms and of the contact rows is issued here, at
+  // clamped indices (entry 0 of a table is always storage, also of an empty one) and in two batches:
+  // the reads indexed by the lane, then the reads indexed by what the first batch and con_pair returned.
+  // The arms below select from these values; none of them waits for a load of its own.
+  const bool lim = !(m.disableflags & DSBL_LIMIT);
+  const int ncon = s.ncon;
+  const bool a_fl = lane < nfl, a_jn = lim && lane < m.njnt, a_tn = lim && lane < m.ntendon;
+  const int i_fl = a_fl ? lane : 0, i_jn = a_jn ? lane : 0, i_tn = a_tn ? lane : 0;
+  int h_pair[NCH];
+#pragma unroll
+  for (int h = 0; h < NCH; h++) {
+    const int c = lane + 64 * h;
+    const int pr = s.con_pair[c < ncon ? c : 0];
+    h_pair[h] = c < ncon ? pr : 0;
+  }
+  const int h_fld0 = MD(fl_dof, i_fl);
+  const int h_jlim = MD(jnt_limited, i_jn);
+  const int h_tlim = MD(ten_limited, i_tn), h_td0 = MD(ten_d0, i_tn), h_td1 = MD(ten_d1, i_tn);
+  const double h_jr0 = MD(jnt_range64, 2 * i_jn), h_jr1 = MD(jnt_range64, 2 * i_jn + 1), h_jmg = MD(jnt_margin64, i_jn);
+  const double h_tc0 = MD(ten_c0_64, i_tn), h_tc1 = MD(ten_c1_64, i_tn), h_tmg = MD(ten_margin64, i_tn);
+  const double h_tr0 = MD(ten_range64, 2 * i_tn), h_tr1 = MD(ten_range64, 2 * i_tn + 1);
+  const float h_jiw = MD(dof_invweight0, i_jn);
+  const float h_tv0 = MD(ten_c0, i_tn), h_tv1 = MD(ten_c1, i_tn), h_tiw = MD(ten_invweight0, i_tn);
+  // second batch
+  const int h_fld = a_fl ? h_fld0 : 0;
+  const float h_floss = MD(dof_frictionloss, h_fld), h_fiw = MD(dof_invweight0, h_fld);
+  int h_dim[NCH], h_root1[NCH], h_root2[NCH];
+  float h_tran[NCH], h_rot[NCH], h_mg[NCH], h_gap[NCH], h_f0[NCH], h_f1[NCH];
+  unsigned long long h_m1[NCH], h_m2[NCH];
+#pragma unroll
+  for (int h = 0; h < NCH; h++) {
+    const int pair = h_pair[h];
+    h_dim[h] = MD(cp_condim, pair);
+    h_tran[h] = MD(cp_tran, pair); h_rot[h] = MD(cp_rot, pair);
+    h_mg[h] = MD(cp_margin, pair); h_gap[h] = MD(cp_gap, pair);
+    h_f0[h] = MD(cp_friction, 5 * pair); h_f1[h] = MD(cp_friction, 5 * pair + 1);
+    h_m1[h] = MD(cp_mask1, pair); h_m2[h] = MD(cp_mask2, pair);
+    h_root1[h] = MD(cp_root1, pair); h_root2[h] = MD(cp_root2, pair);
+  }
+  // frictionloss rows (dof order)
+  if (a_fl) {
+    const int d = h_fld;
+    s.efc_type[lane] = C_FRIC_DOF; s.efc_id[lane] = d;
+    s.efc_i0[lane] = d; s.efc_i1[lane] = -1; s.efc_v0[lane] = 1.f; s.efc_v1[lane] = 0.f;
+    // (aw_set_fault kind 2, the parity classifier's negative test: one row held in the stick state)
+    s.rowbuf[lane] = 0.f; s.efc_floss[lane] = lane == m.fault_flrow ? 1e6f : h_floss;
+    s.efc_force[lane] = h_fiw;
+  }
+  // joint limits: lower then upper per joint, joints in order.  MuJoCo activates a side when
+  // dist = side * (range - q) < margin, in fp64.  That test is evaluated here in fp64 too, on the
+  // fp32 state with the model's fp64 range / margin (jnt_range64): a joint resting on a range
+  // edge equal to its margin (hammer's nail: range edge 0.01 = margin, q ~ 1e-22) is then decided
+  // exactly as the reference decides it -- in fp32, range - q rounds the other way.  dlo / dhi
+  // are dist - margin.
+  int lo = 0, hi = 0;
+  float dlo = 0, dhi = 0;
+  if (a_jn && h_jlim) {
+    const double q = qpos64(s, lane), mgd = h_jmg;
+    const double d0 = __dsub_rn(q, h_jr0);
+    const double d1 = __dsub_rn(h_jr1, q);
+    lo = d0 < mgd; hi = d1 < mgd;
+    dlo = (float)(d0 - mgd); dhi = (float)(d1 - mgd);
+  }
+  int njl;
+  int off = nfl + wave_excl_scan<2>(lo + hi, lane, &njl);
+  if (lo || hi) {
+    for (int side = 0; side < 2; side++) {
+      if (!(side ? hi : lo)) continue;
+      int r = off++;
+      if (r >= EFC_CAP) { atomicOr(&s.status, (unsigned)ST_EFC_OVERFLOW); continue; }
+      s.efc_type[r] = C_LIM_JNT; s.efc_id[r] = lane;
+      s.efc_i0[r] = lane; s.efc_i1[r] = -1; s.efc_v0[r] = side ? -1.f : 1.f; s.efc_v1[r] = 0.f;
+      s.rowbuf[r] = side ? dhi : dlo; s.efc_floss[r] = 0.f; s.efc_force[r] = h_jiw;
+    }
+  }
+  // tendon limits
+  lo = hi = 0;
+  if (a_tn && h_tlim) {
+    const int d1 = h_td1;
+    // fixed tendon length in fp64 with the reference's operation order (no contraction)
+    const double len = __dadd_rn(__dmul_rn(h_tc0, qpos64(s, h_td0)),
+                                 d1 >= 0 ? __dmul_rn(h_tc1, qpos64(s, d1)) : 0.0);
+    const double mgd = h_tmg;
+    const double e0 = __dsub_rn(len, h_tr0);
+    const double e1 = __dsub_rn(h_tr1, len);
+    lo = e0 < mgd; hi = e1 < mgd;
+    dlo = (float)(e0 - mgd); dhi = (float)(e1 - mgd);
+  }
+  int ntl;
+  off = nfl + njl + wave_excl_scan<2>(lo + hi, lane, &ntl);
+  if (lo || hi) {
+    for (int side = 0; side < 2; side++) {
+      if (!(side ? hi : lo)) continue;
+      int r = off++;
+      if (r >= EFC_CAP) { atomicOr(&s.status, (unsigned)ST_EFC_OVERFLOW); continue; }
+      float sg = side ? -1.f : 1.f;
+      s.efc_type[r] = C_LIM_TEN; s.efc_id[r] = lane;
+      s.efc_i0[r] = h_td0; s.efc_i1[r] = h_td1;
+      s.efc_v0[r] = sg * h_tv0; s.efc_v1[r] = sg * h_tv1;
+      s.rowbuf[r] = side ? dhi : dlo; s.efc_floss[r] = 0.f; s.efc_force[r] = h_tiw;
+    }
+  }
+#else
   // frictionloss rows (dof order)
   if (lane < nfl) {
     int d = MD(fl_dof, lane);
@@ -351,12 +465,15 @@ AW_DEV void stage_constraints(const DModel& m, Env& s, int lane) {
       s.rowbuf[r] = side ? dhi : dlo; s.efc_floss[r] = 0.f; s.efc_force[r] = MD(ten_invweight0, lane);
     }
   }
+#endif
   int nsparse = nfl + njl + ntl;
   if (nsparse > EFC_CAP) nsparse = EFC_CAP;
   // contacts: dense rows, lane = contact in chunks of 64 (one chunk in the fast tier).  A contact
   // is kept only if its rows fit: the row offsets are prefix sums, so the kept contacts are a
   // prefix of the list (mj_makeConstraint stops at the first one that does not fit).
+#if !AW_CS_HEAD
   const int ncon = s.ncon;
+#endif
   int nd = 0, dbase = 0;
   int c_dim[NCH], c_pair[NCH], c_r0[NCH];
   static_assert(2 * (6 - 1) < 16, "rows per contact (condim <= 6) fit the scan's 4 bits");
@@ -365,8 +482,13 @@ AW_DEV void stage_constraints(const DModel& m, Env& s, int lane) {
     const int c = lane + 64 * h;
     int dim = 0, nr = 0, pair = 0;
     if (c < ncon) {
+#if AW_CS_HEAD
+      pair = h_pair[h];
+      dim = h_dim[h];
+#else
       pair = s.con_pair[c];
       dim = MD(cp_condim, pair);
+#endif
       nr = dim == 1 ? 1 : 2 * (dim - 1);
     }
     int ntot;
@@ -381,15 +503,24 @@ AW_DEV void stage_constraints(const DModel& m, Env& s, int lane) {
     if (c < ncon && !inc) atomicOr(&s.status, (unsigned)ST_EFC_OVERFLOW);
     if (c < ncon) s.con_efc[c] = inc ? nsparse + doff : -1;
     if (inc) {
+#if AW_CS_HEAD
+      const float tran = h_tran[h], rot = h_rot[h];
+      float pm = s.con_dist[c] - (h_mg[h] - h_gap[h]);
+#else
       const float tran = MD(cp_tran, pair), rot = MD(cp_rot, pair);
       float pm = s.con_dist[c] - (MD(cp_margin, pair) - MD(cp_gap, pair));
+#endif
       int r = nsparse + doff;
       if (dim == 1) {
         s.efc_type[r] = C_CON_FRICTIONLESS; s.efc_id[r] = c; s.rowbuf[r] = pm; s.efc_floss[r] = 0.f;
         s.efc_force[r] = tran; s.efc_i0[r] = 0; s.efc_i1[r] = 0;
       } else {
         for (int k = 1; k < dim; k++) {
+#if AW_CS_HEAD
+          float fri = k == 1 ? h_f0[h] : (k == 2 ? h_f1[h] : MD(cp_friction, 5 * pair + k - 1));
+#else
           float fri = MD(cp_friction, 5 * pair + k - 1);
+#endif
           float dA = tran + fri * fri * (k < 3 ? tran : rot);
           for (int sd = 0; sd < 2; sd++) {
             s.efc_type[r] = C_CON_PYRAMIDAL; s.efc_id[r] = c; s.rowbuf[r] = pm; s.efc_floss[r] = 0.f;
@@ -409,6 +540,12 @@ AW_DEV void stage_constraints(const DModel& m, Env& s, int lane) {
 #pragma unroll
   for (int h = 0; h < NCH; h++) {
     const int cb = 64 * h;
+#if AW_CS_HEAD
+    // carried from the load head (lanes past ncon hold pair 0's values; no lane reads them)
+    const unsigned long long c_m1 = h_m1[h], c_m2 = h_m2[h];
+    const int c_root1 = h_root1[h], c_root2 = h_root2[h];
+    const float c_f0 = h_f0[h], c_f1 = h_f1[h];
+#else
     unsigned long long c_m1 = 0ull, c_m2 = 0ull;
     int c_root1 = 0, c_root2 = 0;
     float c_f0 = 0.f, c_f1 = 0.f;
@@ -418,6 +555,7 @@ AW_DEV void stage_constraints(const DModel& m, Env& s, int lane) {
       c_root1 = MD(cp_root1, pair); c_root2 = MD(cp_root2, pair);
       c_f0 = MD(cp_friction, 5 * pair); c_f1 = MD(cp_friction, 5 * pair + 1);
     }
+#endif
     // (contact, dof) work items flattened over the wave: ceil(ncon NV / 64) passes instead of one
     // per contact (hammer: 33 of 64 lanes busy per contact before); each lane takes its contact's
     // data from the contact's lane by a bpermute.  Same arithmetic per entry (r04w A/B: -1.5 %

@@ -203,12 +203,26 @@ AW_DEV void stage_collision(const DModel& m, Env& s, int lane) {
     for (int h = 0; h < NCH; h++) {
       const int c = lane + 64 * h;
       und[h] = false;
+#if AW_TAIL_HEADS
+      // pair 0 for the lanes past the contacts: the three reads are one clause behind con_pair
+      const bool cv = c < nc0;
+      const int pr0 = s.con_pair[cv ? c : 0];
+      const int pr = cv ? pr0 : 0;
+      const int cls = MD(cp_pack, pr) & 0xff;
+      const float mg = MD(cp_margin, pr);
+      const unsigned long long k64 = MD(cp_kin64, pr);
+      if (cv) {
+        und[h] = (cls == 1 || cls == 2) && fabsf(s.con_dist[c] - mg) <= DEC_EPS;
+        if (und[h]) km |= k64;
+      }
+#else
       if (c < nc0) {
         const int pr = s.con_pair[c];
         const int cls = MD(cp_pack, pr) & 0xff;
         und[h] = (cls == 1 || cls == 2) && fabsf(s.con_dist[c] - MD(cp_margin, pr)) <= DEC_EPS;
         if (und[h]) km |= MD(cp_kin64, pr);
       }
+#endif
     }
     // MPR (cylinder) pairs: the midphase first (fp32 frames, exact distance lower bounds), so
     // that only pairs that can touch request fp64 frames and run fp64 MPR (hammer: the upright
